@@ -22,7 +22,11 @@ no launcher set WORLD_SIZE; under ``torch.distributed.run`` each rank reads RANK
 WORLD_SIZE from the environment.  8 images per rank (scaling "weak").
 
 Prints ONE JSON line (rank 0).  ``value`` = images processed by all ranks / max-over-ranks
-time.  ``roofline`` is for the dominant kernel (the ratio predictor's 3x3 128->256 conv,
+time, ``ms_per_step`` = the time of one of the ``--steps`` timed steps.  A plain run sets up,
+warms up, times those steps (N = 1: the step replayed from a HIP graph), writes the last timed
+step's outputs when ``--dump-outputs DIR`` is given, and prints the line.  Everything below is
+measured only with ``--full``.
+``roofline`` is for the dominant kernel (the ratio predictor's 3x3 128->256 conv,
 k_rp_conv5_v4), timed with HIP events on its launch stream over this run's eager timed steps;
 ``kernels`` carries the same for K5 and the whole step's t_ideal / t_measured.
 ``cpu_baseline`` = the oracle (PyTorch-CPU fp32 restatement of the reference, tests-only
@@ -133,8 +137,22 @@ def parse(argv=None):
                          "rate and the per-kernel HIP-event timings come from an eager pass beside it")
     ap.add_argument("--pipeline-report", type=int, default=0,
                     help="N=1: also time the captured step software-pipelined across batches (pipelined_img_s)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else this benchmark measures or checks: the eager "
+                         "pass with the per-kernel HIP events (kernel_ms, roofline, kernels), the N > 1 scaling "
+                         "baseline and the legs the options above select (inference, C5 stream, parity, whole "
+                         "model, pipelined step, CPU baseline); without it none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single process only: write what the timed step returned in its last timed step (the hot "
+                         "path's four output features) as DIR/<name>.npy, float32 (see sample_outputs)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.gpus > 1 or args.ddp or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs writes the single-process step's outputs: not with --gpus N > 1, --ddp 1 or "
+                 "under a multi-rank launcher")
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -375,7 +393,10 @@ def make_step(ctx, world, inference=False, graph=False, pipeline=False, ddp=None
     return step
 
 
-def timed(step, steps, warmup, world, on_start=None, ddp=None):
+def timed(step, steps, warmup, world, on_start=None, ddp=None, last=None):
+    """Seconds of ``steps`` calls of ``step`` after ``warmup`` untimed ones (N > 1: the slowest
+    rank's).  ``last``: a list that receives what the last timed call returned; no other step's
+    outputs are kept, so without it the steps run exactly as if their results were discarded."""
     ddp = world > 1 if ddp is None else ddp
     for _ in range(warmup):
         step()
@@ -385,9 +406,12 @@ def timed(step, steps, warmup, world, on_start=None, ddp=None):
     if ddp:
         dist.barrier()
     torch.cuda.synchronize()
+    keep = last is not None and steps > 0
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if keep else steps):
         step()
+    if keep:
+        last.append(step())
     torch.cuda.synchronize()
     if ddp:
         dist.barrier()
@@ -399,6 +423,34 @@ def timed(step, steps, warmup, world, on_start=None, ddp=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: 8 MiB of float32, 32 MiB for the step's four features
+
+
+def sample_outputs(feats):
+    """{name: float32 array} of what the timed step returned (the hot path's four output
+    features, ``feature0`` .. ``feature3``), copied off the device at once: a captured step's
+    outputs are static tensors that the next replay overwrites.  An output of more than
+    DUMP_MAX_ELEMS elements is stored as a fixed sample of that many of its (flattened) elements,
+    at the sorted indices ``numpy.random.default_rng(k).choice(numel, DUMP_MAX_ELEMS, False)`` for
+    output k, so two runs with the same arguments store the same elements."""
+    out = {}
+    for k, t in enumerate(feats):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(k).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[f"feature{k}"] = flat.float().cpu().numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: ``path``/<name>.npy, one float32 file per array of sample_outputs."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(path / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ------------------------------------------------------------------ side measurements
@@ -905,19 +957,26 @@ def main():
     if ddp:  # DDP construction: rank 0's parameters and buffers everywhere
         broadcast_parameters([ctx["rp"], ctx["dg"]] + ctx["dsams"])
     step = make_step(ctx, world, ddp=ddp)
-    # eager pass: per-kernel HIP-event timing over its timed steps only
-    dt_eager = timed(step, args.steps, args.warmup, world, on_start=lambda: L.rgbd_timing_enable(1), ddp=ddp)
-    timings = read_timings(L)
-    L.rgbd_timing_enable(0)
+    dt_eager, timings = None, None
+    if args.full:
+        # eager pass: per-kernel HIP-event timing over its timed steps only
+        dt_eager = timed(step, args.steps, args.warmup, world, on_start=lambda: L.rgbd_timing_enable(1), ddp=ddp)
+        timings = read_timings(L)
+        L.rgbd_timing_enable(0)
     use_graph = bool(args.graph) and not ddp
-    # the line's number: the captured step at N = 1; at N > 1 the eager step timed again with the
-    # per-kernel HIP events off (they cost ~0.3 ms of host time per step: 3.23 vs 2.92 ms,
-    # profiles/r05_v2/prof_host.txt)
-    dt = (timed(make_step(ctx, world, graph=True), args.steps, args.warmup, world) if use_graph
-          else timed(step, args.steps, 1, world, ddp=ddp))
+    # what the line's step returned in its last timed step, kept only for --dump-outputs (single
+    # process only, see parse)
+    want = args.dump_outputs is not None
+    last = [] if want else None
+    # the line's number: the captured step at N = 1; otherwise the eager step with the per-kernel
+    # HIP events off (they cost ~0.3 ms of host time per step: 3.23 vs 2.92 ms,
+    # profiles/r05_v2/prof_host.txt), warmed up by the eager pass above when that ran
+    dt = (timed(make_step(ctx, world, graph=True), args.steps, args.warmup, world, last=last) if use_graph
+          else timed(step, args.steps, 1 if args.full else args.warmup, world, ddp=ddp, last=last))
+    dumped = sample_outputs(last.pop()) if want else None
     # the same captured step software-pipelined across batches (make_parts ``pipeline``)
     dt_pipe = timed(make_step(ctx, world, graph=True, pipeline=True), args.steps, args.warmup, world) \
-        if use_graph and args.pipeline_report else None
+        if args.full and use_graph and args.pipeline_report else None
     # N > 1 (RCCL): the step with its collectives inside one HIP graph (serial exchange after the
     # backward), timed beside the eager overlapped step; the line takes the faster of the two
     dt_capt, capt_why, dt_capt_ov, capt_ov_why = None, None, None, None
@@ -941,26 +1000,12 @@ def main():
         if dtc is not None and dtc < dt:
             dt, use_graph, ddp_form = dtc, True, form
     # the same eager step with no collective on every rank at once: the line's own scaling reference
-    dt_local = timed(make_step(ctx, 1), args.steps, args.warmup, world, ddp=ddp) if ddp else None
+    dt_local = timed(make_step(ctx, 1), args.steps, args.warmup, world, ddp=ddp) if ddp and args.full else None
     B = args.batch
     step_ms = dt / args.steps * 1e3
-    raw, per, fracs = kernel_fractions(timings, ctx, B, args.height, args.width, step_ms, world, args.steps)
-    conv_ms, conv_launches = raw["rp_conv3x3"]
     value = B * world * args.steps / dt
-    inf = None
-    if args.inference:
-        istep = make_step(ctx, world, inference=True)
-        idt = timed(istep, args.steps, args.warmup, world, ddp=ddp)
-        inf = round(B * world * args.steps / idt, 2)
-        for m in [ctx["rp"], ctx["dg"]] + ctx["dsams"]:
-            m.train()
-    conv_avg_ms = conv_ms / max(conv_launches, 1)
-    flop = CONV5_FLOP_PER_PX * B * args.height * args.width
-    achieved = flop / (conv_avg_ms * 1e-3) / 1e12
-    default_shape = (B, args.height, args.width, args.dtype) == (8, 480, 640, "bf16")
-    traffic = pmc_traffic(CONV5_KERNEL, default_shape)
-    prof = profile_avg_ns(CONV5_KERNEL, default_shape)
-    achieved_prof = None if prof is None else flop / (prof[0] * 1e-9) / 1e12
+    if want:
+        write_outputs(args.dump_outputs, dumped)
     out = {
         "metric": "NYUv2 640x480 RGB-D img/s (fwd+bwd) of the DGGM+E-DSAM hot path",
         "value": round(value, 2),
@@ -987,18 +1032,6 @@ def main():
                       "no gradient-norm clip: the reference Trainer's max_grad_norm=1.0 clips the norm of the whole "
                       "model's gradients (37.3 M parameters, most of them outside this path)"),
         "graph": use_graph,
-        "eager_img_s": round(B * world * args.steps / dt_eager, 2),
-        "eager_note": ("eager_img_s: the eager pass with the per-kernel HIP events on (the kernel_ms figures); at "
-                       "N > 1 the line's value is the eager step timed again with them off"),
-        "pipelined_img_s": None if dt_pipe is None else round(B * world * args.steps / dt_pipe, 2),
-        "pipelined_note": ("the captured step with the next batch's ratio predictor on a second stream beside this "
-                           "batch's DSAM / DGGM forward, backward and AdamW (bitwise the sequential schedule's "
-                           "parameters: the predictor is forward-only and frozen, Q2)"),
-        "scaling_baseline_img_s": (None if dt_local is None else round(B * world * args.steps / dt_local, 2)),
-        "scaling_baseline_note": ("N > 1: scaling_baseline_img_s = the eager step with no all-reduce / broadcast on "
-                                  "every rank at once, so value / scaling_baseline_img_s is the cost of the "
-                                  "data-parallel exchange; the N=1 line replays a HIP graph (its eager_img_s is the "
-                                  "eager N=1 rate)"),
         "ddp_form": ddp_form,
         "ddp_captured_img_s": None if dt_capt is None else round(B * world * args.steps / dt_capt, 2),
         "ddp_captured_overlap_img_s": None if dt_capt_ov is None else round(B * world * args.steps / dt_capt_ov, 2),
@@ -1012,28 +1045,59 @@ def main():
                               "backward's two streams (ddp_overlapped_eager_img_s)"
                               + ("" if capt_why is None else f"; serial form not captured: {capt_why}")
                               + ("" if capt_ov_why is None else f"; overlapped form not captured: {capt_ov_why}")),
-        "inference_img_s": inf,
-        "kernel_ms": per,
-        "roofline": {"bound": "mfma", "kernel": "k_rp_conv5_v4 (3x3 128->256, custom_model.py:1413)",
-                     "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4),
-                     "events_avg_us": round(conv_avg_ms * 1e3, 2), "events_launches": conv_launches,
-                     "frac_profile": None if achieved_prof is None else round(achieved_prof / MFMA_BF16_PEAK_TFLOPS, 4),
-                     "profile_avg_us": None if prof is None else round(prof[0] / 1e3, 2),
-                     "profile_source": None if prof is None else prof[1],
-                     "profile_vs_events": None if prof is None else round(prof[0] / 1e6 / conv_avg_ms, 4),
-                     "traffic": None if traffic is None else round(traffic[0]),
-                     "traffic_unit": "bytes/launch", "traffic_source": None if traffic is None else traffic[1],
-                     "algorithmic_bytes": (128 + 256) * 2 * B * args.height * args.width,
-                     "timing": ("achieved / frac: conv5's algorithmic FLOP per launch over its average duration "
-                                "measured in THIS run by HIP events around each conv5 launch on its stream over the "
-                                "eager timed steps (events_launches launches, no profiler attached); frac_profile: "
-                                "the same FLOP over the average in the committed rocprofv3 trace of this tree's "
-                                "bench step (profile_source, bench.EVIDENCE_DIR; the profiler costs the kernel a "
-                                "few per cent, DESIGN.md §5.8.1); profile_vs_events = the two averages' ratio")},
-        "kernels": fracs,
     }
-    if rank == 0 and args.parity:
+    if args.full:
+        raw, per, fracs = kernel_fractions(timings, ctx, B, args.height, args.width, step_ms, world, args.steps)
+        conv_ms, conv_launches = raw["rp_conv3x3"]
+        inf = None
+        if args.inference:
+            istep = make_step(ctx, world, inference=True)
+            idt = timed(istep, args.steps, args.warmup, world, ddp=ddp)
+            inf = round(B * world * args.steps / idt, 2)
+            for m in [ctx["rp"], ctx["dg"]] + ctx["dsams"]:
+                m.train()
+        conv_avg_ms = conv_ms / max(conv_launches, 1)
+        flop = CONV5_FLOP_PER_PX * B * args.height * args.width
+        achieved = flop / (conv_avg_ms * 1e-3) / 1e12
+        default_shape = (B, args.height, args.width, args.dtype) == (8, 480, 640, "bf16")
+        traffic = pmc_traffic(CONV5_KERNEL, default_shape)
+        prof = profile_avg_ns(CONV5_KERNEL, default_shape)
+        achieved_prof = None if prof is None else flop / (prof[0] * 1e-9) / 1e12
+        out.update({
+            "eager_img_s": round(B * world * args.steps / dt_eager, 2),
+            "eager_note": ("eager_img_s: the eager pass with the per-kernel HIP events on (the kernel_ms figures); at "
+                           "N > 1 the line's value is the eager step timed again with them off"),
+            "pipelined_img_s": None if dt_pipe is None else round(B * world * args.steps / dt_pipe, 2),
+            "pipelined_note": ("the captured step with the next batch's ratio predictor on a second stream beside this "
+                               "batch's DSAM / DGGM forward, backward and AdamW (bitwise the sequential schedule's "
+                               "parameters: the predictor is forward-only and frozen, Q2)"),
+            "scaling_baseline_img_s": (None if dt_local is None else round(B * world * args.steps / dt_local, 2)),
+            "scaling_baseline_note": ("N > 1: scaling_baseline_img_s = the eager step with no all-reduce / broadcast on "
+                                      "every rank at once, so value / scaling_baseline_img_s is the cost of the "
+                                      "data-parallel exchange; the N=1 line replays a HIP graph (its eager_img_s is the "
+                                      "eager N=1 rate)"),
+            "inference_img_s": inf,
+            "kernel_ms": per,
+            "roofline": {"bound": "mfma", "kernel": "k_rp_conv5_v4 (3x3 128->256, custom_model.py:1413)",
+                         "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4),
+                         "events_avg_us": round(conv_avg_ms * 1e3, 2), "events_launches": conv_launches,
+                         "frac_profile": None if achieved_prof is None else round(achieved_prof / MFMA_BF16_PEAK_TFLOPS, 4),
+                         "profile_avg_us": None if prof is None else round(prof[0] / 1e3, 2),
+                         "profile_source": None if prof is None else prof[1],
+                         "profile_vs_events": None if prof is None else round(prof[0] / 1e6 / conv_avg_ms, 4),
+                         "traffic": None if traffic is None else round(traffic[0]),
+                         "traffic_unit": "bytes/launch", "traffic_source": None if traffic is None else traffic[1],
+                         "algorithmic_bytes": (128 + 256) * 2 * B * args.height * args.width,
+                         "timing": ("achieved / frac: conv5's algorithmic FLOP per launch over its average duration "
+                                    "measured in THIS run by HIP events around each conv5 launch on its stream over the "
+                                    "eager timed steps (events_launches launches, no profiler attached); frac_profile: "
+                                    "the same FLOP over the average in the committed rocprofv3 trace of this tree's "
+                                    "bench step (profile_source, bench.EVIDENCE_DIR; the profiler costs the kernel a "
+                                    "few per cent, DESIGN.md §5.8.1); profile_vs_events = the two averages' ratio")},
+            "kernels": fracs,
+        })
+    if args.full and rank == 0 and args.parity:
         out["parity"] = parity(dev)
         out["parity"]["bf16"] = parity(dev, torch.bfloat16)
         # the same with the reference's float32 ratio: the bf16 error with no flipped decision
@@ -1044,11 +1108,11 @@ def main():
         out["parity"]["bf16_attrib_colour_rounding"] = parity(dev, fixture="g7", colour_bf16=True)
         out["parity"]["bf16_attrib_colour_and_output_rounding"] = parity(dev, fixture="g7", colour_bf16=True,
                                                                         out_bf16=True)
-    if rank == 0 and world == 1 and args.c5_stream:
+    if args.full and rank == 0 and world == 1 and args.c5_stream:
         out["c5_stream"] = c5_stream(ctx)
-    if rank == 0 and world == 1 and args.full_model:
+    if args.full and rank == 0 and world == 1 and args.full_model:
         out["full_model"] = full_model(dev)
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(ctx, args)
     if rank == 0:
         print(json.dumps(out), file=line_out, flush=True)

@@ -45,7 +45,7 @@ def test_bench_launcher_json(world, H, W, backend):
     overlapped all-reduces and their stream waits and the buffer broadcasts on a one-GPU box."""
     _need_devices(backend, world)
     extra = ["--ddp", "1"] if world == 1 else []
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), *extra, "--backend", backend, "--steps", "2",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), *extra, "--full", "--backend", backend, "--steps", "2",
                         "--warmup", "1", "--cpu-baseline", "0", "--c5-stream", "0", "--inference", "0", "--parity", "0",
                         "--height", str(H), "--width", str(W)],
                        capture_output=True, text=True, timeout=380, cwd=REPO)

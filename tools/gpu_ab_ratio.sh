@@ -13,6 +13,6 @@ if [ -n "$AB" ]; then
   tail -3 "$O/ab.txt"
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 600 python bench.py $BENCH > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+  timeout -k 10 600 python bench.py --full $BENCH > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench.json'));print('bench',d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline'].get('events_avg_us'),d['kernels']['k5_dsam']['ms_per_step'],d.get('inference_img_s'))"
 fi
