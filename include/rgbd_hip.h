@@ -191,6 +191,19 @@ typedef struct rgbd_nhwc_job {
   int B, C, H, W;
 } rgbd_nhwc_job;
 int rgbd_nchw_to_nhwc_multi(int n, const rgbd_nhwc_job* jobs, void* stream);  /* jobs: host array */
+/* Up to four float32-source conversions in one launch (the float32-interface bf16 mode of the
+ * hot path: colour map 0 -> bf16 and colour maps 1..3 -> float32 in the forward, the upstream
+ * gradients G[3], G[2], G[1] -> bf16 in the backward).  Each job reads float32 [B][C][H][W] and
+ * writes [B][H][W][C] as dst_dtype: RGBD_BF16 (one round-to-nearest-even per element, as
+ * torch's .to(bfloat16)) or RGBD_F32 (a bitwise copy).  C % 8 == 0 (RGBD_E_SHAPE otherwise), any
+ * H * W; src and dst 16-byte aligned (RGBD_E_ARG otherwise); another dst_dtype: RGBD_E_DTYPE. */
+typedef struct rgbd_nhwc_job_f32 {
+  const void* src;  /* [B][C][H][W] float32 (device) */
+  void* dst;        /* [B][H][W][C] dst_dtype (device) */
+  int B, C, H, W;
+  int dst_dtype;    /* RGBD_BF16 or RGBD_F32 */
+} rgbd_nhwc_job_f32;
+int rgbd_nchw_to_nhwc_multi_f32(int n, const rgbd_nhwc_job_f32* jobs, void* stream);  /* jobs: host array */
 /* Packs DSAModule weights (conv_layers[0..3].weight, rgb_projection.weight; float32
  * [4][Cout][Cin][3][3] and [Cout][Cin][3][3]) into the implicit-GEMM B operands.
  * RGBD_F32 (segment form):
@@ -230,6 +243,20 @@ int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd
 int rgbd_dsam_fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
                        int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
                        const void* residual_nhwc, void* out_nhwc, void* ws, void* stream);
+/* rgbd_dsam_fwd_nhwc with a float32 interface (compute dtype RGBD_BF16, anything else:
+ * RGBD_E_DTYPE; the operands x_nhwc / wfwd stay bf16): with v = acc + bias, the float32 value the
+ * epilogue holds before the residual,
+ *   out_f32_nhwc (float32 [B][ho][wo][Cout], optional) = residual_f32_nhwc + v   (one float32 add)
+ *   out_nhwc     (bf16    [B][ho][wo][Cout], optional) = RNE(out_f32_nhwc)       (one rounding)
+ * residual_f32_nhwc: float32 [B][ho][wo][Cout], optional (NULL: v itself).  At least one output;
+ * both float32 pointers 16-byte aligned.  A bf16 residual_nhwc is accepted only with both float32
+ * pointers NULL, and the call is then rgbd_dsam_fwd_nhwc (RGBD_E_ARG otherwise).  With a residual
+ * whose values are bf16-representable, out_nhwc is bitwise rgbd_dsam_fwd_nhwc's.  Workspace,
+ * plans (RGBD_LEG_FWD) and argument checks are those of rgbd_dsam_fwd_nhwc[_planned]. */
+int rgbd_dsam_fwd_nhwc_f32io(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
+                             int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
+                             const void* residual_nhwc, void* out_nhwc, void* ws, void* stream,
+                             const float* residual_f32_nhwc, float* out_f32_nhwc);
 /* dX of one DSAModule, plus the upstream gradient of its input's other consumer:
  *   dx = gin + sum_i m_i * ConvT_i(gout) + ConvT_proj(gout)
  * gout_nhwc: dtype [B][ho][wo][Cout].  At least one of dx_nchw (dtype [B][Cin][h][w]) and
@@ -273,6 +300,11 @@ int rgbd_dsam_fwd_nhwc_planned(int dtype, const void* x_nhwc, const uint8_t* cod
                                const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
                                const void* wfwd, const float* bias, const void* residual_nhwc,
                                void* out_nhwc, const void* plan, void* ws, void* stream);
+int rgbd_dsam_fwd_nhwc_f32io_planned(int dtype, const void* x_nhwc, const uint8_t* code,
+                                     const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
+                                     const void* wfwd, const float* bias, const void* residual_nhwc, void* out_nhwc,
+                                     const void* plan, void* ws, void* stream, const float* residual_f32_nhwc,
+                                     float* out_f32_nhwc);
 int rgbd_dsam_bwd_data_planned(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin,
                                int h, int w, int Cout, const void* wbwd, const void* gin_nchw,
                                const void* gin_nhwc, void* dx_nchw, void* dx_nhwc, const void* plan,

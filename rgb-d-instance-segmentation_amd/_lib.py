@@ -61,6 +61,7 @@ SIGNATURES = {
     "rgbd_dggm_fuse_bwd_multi": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P, _P]),
     "rgbd_nchw_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "rgbd_nchw_to_nhwc_multi": (_I, [_I, _P, _P]),
+    "rgbd_nchw_to_nhwc_multi_f32": (_I, [_I, _P, _P]),
     "rgbd_adamw_multi": (_I, [_I, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, ctypes.c_double, _P]),
     "rgbd_adamw_multi_shadow": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
@@ -78,6 +79,9 @@ SIGNATURES = {
     "rgbd_dsam_run_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "rgbd_dsam_plan": (_I, [_I, _P, _P]),
     "rgbd_dsam_fwd_nhwc_planned": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_fwd_nhwc_f32io": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_fwd_nhwc_f32io_planned": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P]),
     "rgbd_dsam_bwd_data_planned": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rgbd_dsam_bwd_weight_planned": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rgbd_dsam_bwd_weight_planned_multi": (_I, [_I, _P, _P, _P]),

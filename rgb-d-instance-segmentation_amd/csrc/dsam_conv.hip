@@ -56,6 +56,9 @@ struct ConvArgs {
   float* partial;                   // bf16: partial tiles of multi-chunk tiles (reduced by their last chunk)
   const bf16_t* zero;               // bf16: LD_ZERO_BYTES of zeros (zeroed by k_dsam_plan)
   unsigned long long* stamps;       // diagnostics only (rgbd_debug_dsam_stamps); null otherwise
+  // the F32IO instantiation of k_dsam_lds only (forward, NHWC-only epilogue):
+  const float* residual_f32_nhwc;   // optional float32 NHWC residual (instead of residual_nhwc)
+  float* out_f32_nhwc;              // optional float32 NHWC copy of the result before its rounding
 };
 
 constexpr int BM = 64, BN = 64;
@@ -451,6 +454,78 @@ __global__ __launch_bounds__(256) void k_nchw_to_nhwc_multi(const NhwcJobs J) {
     const int p = p0 + pl, c = c0 + cl;
     if (p < HW && c < C)
       *reinterpret_cast<uint4*>(dst + ((long long)b * HW + p) * C + c) = *reinterpret_cast<const uint4*>(&tile[pl][cl]);
+  }
+}
+
+// The same for float32 sources (the float32-interface bf16 mode: colour maps in the forward,
+// upstream gradients in the backward): each job's NHWC copy is bf16 (one RNE rounding) or float32.
+// 64 x 64 tiles again; loads take 4 pixels of one channel (16 bytes; one by one when HW % 4),
+// the LDS image is [pixel][channel] f32 with rows of 65 words (the transposing writes and the
+// row reads both land on 64 distinct banks), stores take 8 channels of one pixel: one 16-byte
+// store in bf16, two in float32.
+struct NhwcJobsF32 {
+  const float* src[NHWC_MAXJOB];
+  void* dst[NHWC_MAXJOB];
+  int C[NHWC_MAXJOB], HW[NHWC_MAXJOB], tp[NHWC_MAXJOB], tc[NHWC_MAXJOB], f32[NHWC_MAXJOB];
+  int block0[NHWC_MAXJOB + 1];  // first block of each job; block0[n] = grid
+  int n;
+};
+__global__ __launch_bounds__(256) void k_nchw_to_nhwc_multi_f32(const NhwcJobsF32 J) {
+  __shared__ float tile[64][65];
+  int j = 0;
+#pragma unroll
+  for (int i = 1; i < NHWC_MAXJOB; ++i)
+    if (i < J.n && (int)blockIdx.x >= J.block0[i]) j = i;
+  const float* src = J.src[j];
+  const int C = J.C[j], HW = J.HW[j], per = J.tp[j] * J.tc[j];
+  const int idx = blockIdx.x - J.block0[j], b = idx / per, t = idx - b * per;
+  const int p0 = (t % J.tp[j]) * 64, c0 = (t / J.tp[j]) * 64;
+  const bool vec = (HW & 3) == 0;
+  float4 q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // all four loads in flight together
+    const int v = threadIdx.x + 256 * k, cl = v >> 4, pl = (v & 15) * 4;  // channel, 4-pixel group
+    const int c = c0 + cl, p = p0 + pl;
+    const float* row = src + ((long long)b * C + c) * HW;
+    q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < C) {
+      if (vec) {
+        if (p < HW) q[k] = *reinterpret_cast<const float4*>(row + p);
+      } else {
+        if (p < HW) q[k].x = row[p];
+        if (p + 1 < HW) q[k].y = row[p + 1];
+        if (p + 2 < HW) q[k].z = row[p + 2];
+        if (p + 3 < HW) q[k].w = row[p + 3];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int v = threadIdx.x + 256 * k, cl = v >> 4, pl = (v & 15) * 4;
+    tile[pl][cl] = q[k].x;
+    tile[pl + 1][cl] = q[k].y;
+    tile[pl + 2][cl] = q[k].z;
+    tile[pl + 3][cl] = q[k].w;
+  }
+  __syncthreads();
+  const bool f32 = J.f32[j] != 0;  // workgroup-uniform
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + 256 * k, pl = v >> 3, cl = (v & 7) * 8;  // pixel, 8-channel group
+    const int p = p0 + pl, c = c0 + cl;
+    if (p >= HW || c >= C) continue;
+    float e[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) e[i] = tile[pl][cl + i];
+    const long long o = ((long long)b * HW + p) * C + c;
+    if (f32) {
+      float* d = (float*)J.dst[j] + o;
+      *reinterpret_cast<float4*>(d) = make_float4(e[0], e[1], e[2], e[3]);
+      *reinterpret_cast<float4*>(d + 4) = make_float4(e[4], e[5], e[6], e[7]);
+    } else {
+      *reinterpret_cast<uint4*>((bf16_t*)J.dst[j] + o) =
+          make_uint4(pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]), pack_bf16x2(e[6], e[7]));
+    }
   }
 }
 
@@ -1388,7 +1463,7 @@ __device__ __forceinline__ void ld_stamp(unsigned long long* st, int f) {
 // one fixed pixel block (the copies stay, their sources become L2-resident: the ceiling of
 // locality work).
 // One (tile, chunk) item of k_dsam_lds for N tile ntile (of ntn).
-template <int KC, int NODMA = 0>
+template <int KC, int NODMA = 0, bool F32IO = false>
 __device__ __forceinline__ void ld_item(const ConvArgs& a, int cls, int tile, int chunk, int ntile, int ntn,
                                         int* next_s, int nitems, unsigned long long* st = nullptr) {
   using Cfg = LdCfg<KC>;
@@ -1630,7 +1705,69 @@ __device__ __forceinline__ void ld_item(const ConvArgs& a, int cls, int tile, in
   // ---- epilogue (same contract as k_conv_igemm), staged through LDS in two 96-column halves:
   // pass 1 runs along pixels (NCHW residual loads and stores), pass 2 along channels (NHWC);
   // every thread's loads of a pass are independent and issued together.
-  if (!a.out_nchw) {
+  if constexpr (F32IO) {
+    // NHWC-only epilogue with a float32 interface (the forward cascade of the float32-interface
+    // mode): the one-pass epilogue below with the residual read as float32 (two 16-byte loads
+    // per item, all twelve of a thread in flight across the LDS staging) and res + (acc + bias)
+    // stored twice: as float32 (two 16-byte stores: cp1 as the DGGM pass and the outputs take it)
+    // and rounded once to bf16 (the next DSAM's operand).  Either store may be absent.
+    constexpr int LDE = LD_BN + 4;
+    constexpr int NCH = LD_BN / 8;
+    constexpr int NIT = LD_BM * NCH / 512;
+    static_assert(LD_BM * LDE * 4 <= Cfg::ROWTAB, "epilogue image must not overlap the row tables");
+    float* et = (float*)smem;
+    const float* rf = a.residual_f32_nhwc;
+    float* of = a.out_f32_nhwc;
+    bf16_t* onhwc = (bf16_t*)a.out_nhwc;
+    float4 rv[NIT][2];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int it = tid + 512 * i, ml = it / NCH, n = n0 + 8 * (it % NCH);
+      const int4 ro = rowout[ml];
+      rv[i][0] = rv[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (rf && ro.x >= 0 && n < a.N) {
+        const float* rp = rf + (long long)ro.y * a.N + n;
+        rv[i][0] = *reinterpret_cast<const float4*>(rp);
+        rv[i][1] = *reinterpret_cast<const float4*>(rp + 4);
+      }
+    }
+    __syncthreads();  // ring reads done
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int nj = 0; nj < 3; ++nj)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          et[(wm * 64 + 16 * mi + 4 * g + reg) * LDE + wn * 48 + 16 * nj + r] = acc[mi][nj][reg];
+    __syncthreads();
+    fetch_word();
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int it = tid + 512 * i, ml = it / NCH, nl = 8 * (it % NCH), n = n0 + nl;
+      const int4 ro = rowout[ml];
+      if (ro.x < 0 || n >= a.N) continue;
+      const float4 e0 = *reinterpret_cast<const float4*>(et + ml * LDE + nl);
+      const float4 e1 = *reinterpret_cast<const float4*>(et + ml * LDE + nl + 4);
+      float v[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+      const float rr[8] = {rv[i][0].x, rv[i][0].y, rv[i][0].z, rv[i][0].w, rv[i][1].x, rv[i][1].y, rv[i][1].z, rv[i][1].w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += bsum[ro.z * LD_BN + nl + e];
+      if (rf)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = rr[e] + v[e];
+      const long long o = (long long)ro.y * a.N + n;
+      if (of) {
+        *reinterpret_cast<float4*>(of + o) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(of + o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      }
+      if (onhwc)
+        *reinterpret_cast<uint4*>(onhwc + o) =
+            make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+    }
+    ld_stamp(st, 5);
+    publish();
+    return;
+  } else if (!a.out_nchw) {
     // NHWC-only epilogue (the hot path's forward cascade and dX): one pass.  The accumulators go
     // to an LDS image [128 rows][196] f32 (rows = tile pixels; the 4-float pad makes the 4 rows
     // a wave writes per register land on disjoint banks), then each thread owns 6 (row, 8-channel)
@@ -1798,7 +1935,7 @@ __device__ __forceinline__ void ld_item(const ConvArgs& a, int cls, int tile, in
 // Persistent: grid (workgroups, N tiles); each workgroup takes the next item of its N tile's list
 // from a counter (items differ up to ~5x in steps: dynamic assignment balances the tail; the
 // multi-chunk reductions stay in chunk order, so results do not depend on who ran what).
-template <int KC, bool STAMPS = false, int NODMA = 0>
+template <int KC, bool STAMPS = false, int NODMA = 0, bool F32IO = false>
 __global__ __launch_bounds__(512, 1) void k_dsam_lds(ConvArgs a) {
   using Cfg = LdCfg<KC>;
   extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -1840,7 +1977,7 @@ __global__ __launch_bounds__(512, 1) void k_dsam_lds(ConvArgs a) {
     ld_stamp(st, 0);
     if (st && threadIdx.x == 0) st[7] = (unsigned long long)v;
     // next_s is rewritten only after the item's K loop, behind its prologue barrier
-    ld_item<KC, NODMA>(a, v & 3, v >> 5, (v >> 2) & 7, ntile, gridDim.y, next_s, nitems, st);
+    ld_item<KC, NODMA, F32IO>(a, v & 3, v >> 5, (v >> 2) & 7, ntile, gridDim.y, next_s, nitems, st);
   }
 }
 
@@ -1970,6 +2107,16 @@ hipError_t launch_ld(const ConvArgs& b, dim3 grid, hipStream_t s) {
   k_dsam_lds<KC><<<grid, 512, LdCfg<KC>::SMEM, s>>>(b);
   return hipSuccess;
 }
+// the float32-interface forward (ConvArgs::residual_f32_nhwc / out_f32_nhwc): an instantiation of
+// its own, so the plain one's code does not depend on it
+template <int KC>
+hipError_t launch_ld_f32io(const ConvArgs& b, dim3 grid, hipStream_t s) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)k_dsam_lds<KC, false, 0, true>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LdCfg<KC>::SMEM);
+  if (attr != hipSuccess) return attr;
+  k_dsam_lds<KC, false, 0, true><<<grid, 512, LdCfg<KC>::SMEM, s>>>(b);
+  return hipSuccess;
+}
 
 template <typename T>
 int launch_conv(const ConvArgs& a, hipStream_t s, const void* planned = nullptr) {
@@ -1991,7 +2138,10 @@ int launch_conv(const ConvArgs& a, hipStream_t s, const void* planned = nullptr)
     // persistent: about one workgroup per CU (LDS-bound) over all N tiles
     constexpr int pers = 256;  // persistent: one LDS-bound workgroup per CU
     dim3 grid2(std::max(1, pers / P.ntn), P.ntn, 1);
-    const hipError_t e = P.kc == 3 ? launch_ld<3>(b, grid2, s) : P.kc == 2 ? launch_ld<2>(b, grid2, s) : launch_ld<1>(b, grid2, s);
+    const bool f32io = a.residual_f32_nhwc || a.out_f32_nhwc;
+    const hipError_t e =
+        f32io ? (P.kc == 3 ? launch_ld_f32io<3>(b, grid2, s) : P.kc == 2 ? launch_ld_f32io<2>(b, grid2, s) : launch_ld_f32io<1>(b, grid2, s))
+              : (P.kc == 3 ? launch_ld<3>(b, grid2, s) : P.kc == 2 ? launch_ld<2>(b, grid2, s) : launch_ld<1>(b, grid2, s));
     if (e != hipSuccess) return (int)e;
     RGBD_CHECK_LAUNCH();
     return RGBD_OK;
@@ -2105,6 +2255,41 @@ int rgbd_nchw_to_nhwc_multi(int n, const rgbd_nhwc_job* jobs, void* stream) {
   return RGBD_OK;
 }
 
+int rgbd_nchw_to_nhwc_multi_f32(int n, const rgbd_nhwc_job_f32* jobs, void* stream) {
+  RGBD_REQUIRE(n >= 1 && n <= NHWC_MAXJOB && jobs, RGBD_E_ARG);
+  NhwcJobsF32 J;
+  long long blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const rgbd_nhwc_job_f32& q = jobs[i];
+    RGBD_REQUIRE(q.src && q.dst && q.B > 0 && q.C > 0 && q.H > 0 && q.W > 0, RGBD_E_ARG);
+    RGBD_REQUIRE(q.dst_dtype == RGBD_F32 || q.dst_dtype == RGBD_BF16, RGBD_E_DTYPE);
+    RGBD_REQUIRE(q.C % 8 == 0, RGBD_E_SHAPE);  // 16-byte NHWC stores
+    RGBD_REQUIRE(((uintptr_t)q.src & 15) == 0 && ((uintptr_t)q.dst & 15) == 0, RGBD_E_ARG);  // 16-byte accesses
+    RGBD_REQUIRE((long long)q.H * q.W < (1ll << 31), RGBD_E_SHAPE);
+    J.src[i] = (const float*)q.src;
+    J.dst[i] = q.dst;
+    J.C[i] = q.C;
+    J.HW[i] = q.H * q.W;
+    J.tp[i] = ceil_div((long long)q.H * q.W, 64);
+    J.tc[i] = ceil_div(q.C, 64);
+    J.f32[i] = q.dst_dtype == RGBD_F32;
+    J.block0[i] = (int)blocks;
+    blocks += (long long)q.B * J.tp[i] * J.tc[i];
+  }
+  RGBD_REQUIRE(blocks < (1ll << 31), RGBD_E_SHAPE);
+  for (int i = n; i < NHWC_MAXJOB; ++i) {
+    J.src[i] = nullptr; J.dst[i] = nullptr;
+    J.C[i] = J.HW[i] = J.tp[i] = J.tc[i] = J.f32[i] = 0;
+    J.block0[i] = (int)blocks;
+  }
+  J.block0[n] = (int)blocks;
+  J.block0[NHWC_MAXJOB] = (int)blocks;
+  J.n = n;
+  k_nchw_to_nhwc_multi_f32<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(J);
+  RGBD_CHECK_LAUNCH();
+  return RGBD_OK;
+}
+
 long long rgbd_dsam_packed_elems(int dtype, int Cin, int Cout) {
   if (Cin <= 0 || Cout <= 0) return 0;
   if (dtype == RGBD_F32) return 45ll * Cin * Cout;
@@ -2195,13 +2380,18 @@ int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd
 
 static int fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info, int B,
                     int Cin, int h, int w, int Cout, const void* wfwd, const float* bias, const void* residual_nhwc,
-                    void* out_nhwc, const void* planned, void* ws, void* stream) {
+                    void* out_nhwc, const void* planned, void* ws, void* stream,
+                    const float* residual_f32_nhwc = nullptr, float* out_f32_nhwc = nullptr) {
   RGBD_REQUIRE(dtype == RGBD_BF16, RGBD_E_DTYPE);
-  RGBD_REQUIRE(x_nhwc && code && info && wfwd && bias && out_nhwc && ws, RGBD_E_ARG);
+  RGBD_REQUIRE(x_nhwc && code && info && wfwd && bias && (out_nhwc || out_f32_nhwc) && ws, RGBD_E_ARG);
   RGBD_REQUIRE(B > 0 && h > 0 && w > 0 && Cout > 0 && Cin > 0, RGBD_E_ARG);
+  // the float32-interface kernel takes its residual as float32 only
+  RGBD_REQUIRE(!((residual_f32_nhwc || out_f32_nhwc) && residual_nhwc), RGBD_E_ARG);
+  RGBD_REQUIRE((((uintptr_t)residual_f32_nhwc | (uintptr_t)out_f32_nhwc) & 15) == 0, RGBD_E_ARG);  // 16-byte accesses
   ConvArgs a = fwd_args(B, Cin, h, w, Cout);
   a.x = x_nhwc; a.code = code; a.w = wfwd;
   a.bias4 = bias; a.info = info; a.residual_nhwc = residual_nhwc; a.out_nhwc = out_nhwc;
+  a.residual_f32_nhwc = residual_f32_nhwc; a.out_f32_nhwc = out_f32_nhwc;
   a.partial = (float*)ws;
   return launch_conv<bf16_t>(a, (hipStream_t)stream, planned);
 }
@@ -2217,6 +2407,24 @@ int rgbd_dsam_fwd_nhwc_planned(int dtype, const void* x_nhwc, const uint8_t* cod
   RGBD_REQUIRE(plan, RGBD_E_ARG);
   return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, plan, ws,
                   stream);
+}
+
+int rgbd_dsam_fwd_nhwc_f32io(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
+                             int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
+                             const void* residual_nhwc, void* out_nhwc, void* ws, void* stream,
+                             const float* residual_f32_nhwc, float* out_f32_nhwc) {
+  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, nullptr, ws,
+                  stream, residual_f32_nhwc, out_f32_nhwc);
+}
+int rgbd_dsam_fwd_nhwc_f32io_planned(int dtype, const void* x_nhwc, const uint8_t* code,
+                                     const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
+                                     const void* wfwd, const float* bias, const void* residual_nhwc, void* out_nhwc,
+                                     const void* plan, void* ws, void* stream, const float* residual_f32_nhwc,
+                                     float* out_f32_nhwc) {
+  RGBD_REQUIRE(dtype == RGBD_BF16, RGBD_E_DTYPE);
+  RGBD_REQUIRE(plan, RGBD_E_ARG);
+  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, plan, ws,
+                  stream, residual_f32_nhwc, out_f32_nhwc);
 }
 
 static int bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h, int w, int Cout,

@@ -21,7 +21,7 @@ from transformers.models.mask2former.modeling_mask2former import (Mask2FormerPix
                                                                   Mask2FormerPixelLevelModuleOutput)
 
 from . import deform_attn, dense, mask_predictor, masked_attention, ops, point_loss, swin
-from .hot_path import hot_path, prepare
+from .hot_path import float32_interface, hot_path, prepare
 from .modules import DSAModule, DepthGradientInjectionResidual, EnhancedDepthImageRatioPredictor
 
 SUPPORTED_VERSIONS = ("0.4.0", "0.0.0")
@@ -57,6 +57,9 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
         self.version = version
         # bf16 MFMA for the DSAM / ratio-predictor GEMMs; float32 is the exact parity mode
         self.compute_dtype = torch.float32
+        # None: the hot path's colour maps / cp1 / features in the compute dtype; torch.float32 with
+        # bf16 compute: the float32-interface mode (hot_path.float32_interface)
+        self.interface_dtype = None
         if version == "0.4.0":
             self.ratio_predictor = EnhancedDepthImageRatioPredictor(3)
             self.dsam0 = DSAModule(in_channels=96, out_channels=192, num_depth_regions=3)
@@ -64,8 +67,10 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
             self.dsam2 = DSAModule(in_channels=384, out_channels=768, num_depth_regions=3)
             self.depth_gradient_injection = DepthGradientInjectionResidual([96, 192, 384, 768], 3)
 
-    def set_compute_dtype(self, dtype):
+    def set_compute_dtype(self, dtype, interface=None):
+        float32_interface(dtype, interface)
         self.compute_dtype = dtype
+        self.interface_dtype = interface
         for m in self.modules():
             if hasattr(m, "compute_dtype"):
                 m.compute_dtype = dtype
@@ -76,12 +81,13 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
         ``status_sink``: see hot_path.hot_path (None = raise the reference's ValueError at once)."""
         # the ratio-free part (decomposition modes, bf16 colour layouts) beside the ratio predictor
         prep = prepare(pixel_values, list(color_feature_map), self.compute_dtype,
-                       dsam_modules=[self.dsam0, self.dsam1, self.dsam2])
+                       dsam_modules=[self.dsam0, self.dsam1, self.dsam2], interface_dtype=self.interface_dtype)
         if ratios is None:
             ratios = self.ratio_predictor(pixel_values[:, 3:6])       # :336 (no grad, Q2)
         feats = hot_path(pixel_values, ratios, list(color_feature_map), [self.dsam0, self.dsam1, self.dsam2],
                          self.depth_gradient_injection, dtype=self.compute_dtype,
-                         check_status=status_sink is None, status_sink=status_sink, prepared=prep)
+                         check_status=status_sink is None, status_sink=status_sink, prepared=prep,
+                         interface_dtype=self.interface_dtype)
         dt = color_feature_map[0].dtype
         return [f.to(dt) for f in feats]
 
@@ -158,6 +164,6 @@ class CustomMask2FormerForUniversalSegmentation(Mask2FormerForUniversalSegmentat
         # f1: the class head (built by the HF constructor after the model body was installed)
         dense.install(self.class_predictor)
 
-    def set_compute_dtype(self, dtype):
-        self.model.pixel_level_module.set_compute_dtype(dtype)
+    def set_compute_dtype(self, dtype, interface=None):
+        self.model.pixel_level_module.set_compute_dtype(dtype, interface)
         return self

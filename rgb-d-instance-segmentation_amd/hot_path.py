@@ -14,6 +14,9 @@ Here:
     DGGM gate + final sum in one elementwise pass over all four scales (K2, one launch).
 Backward produces exactly the gradients the reference graph has: DSAM / DGGM parameters,
 nothing for the colour maps (detached) or the ratio (left the graph via .item()).
+Three precision modes: float32; bfloat16 (operands, cp1 and features bf16); and bfloat16 compute
+with a float32 interface (``interface_dtype=torch.float32``: colour maps, cp1 and features float32,
+bf16 only as the DSAM operands; ``float32_interface``).
 """
 import ctypes
 
@@ -138,9 +141,10 @@ class Prepared:
     decomposition (grey plane, histogram, modes: ops.edsam_modes) and, in bf16, the NHWC copies
     of the colour maps — launched on the side stream so they run beside the ratio predictor."""
 
-    def __init__(self, side, pixel_values, modes, colors, nhwc, dtype, sources, packs=None):
+    def __init__(self, side, pixel_values, modes, colors, nhwc, dtype, sources, packs=None, interface_dtype=None):
         self.side, self.pixel_values, self.modes = side, pixel_values, modes
         self.colors, self.nhwc, self.dtype = colors, nhwc, dtype
+        self.interface_dtype = interface_dtype  # as given to prepare() (None: the compute dtype)
         self.packs = packs or {}  # DSAM index -> bf16 packed filters for all 16 codes
         self.sources = sources  # (data_ptr, shape) of the pixel_values and colour maps it was built from
 
@@ -173,21 +177,42 @@ def _pack_all(m, k, dtype):
     return m._pack_cache.get(conv_ws, m.rgb_projection.weight, dtype, code_mask=None, want_bwd=want_bwd)
 
 
-def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_modules=None):
+def float32_interface(dtype, interface_dtype):
+    """Validate a (compute dtype, interface dtype) pair; True for the float32-interface bf16 mode.
+    ``interface_dtype`` None: colour maps, cp1 and outputs in the compute dtype (the float32 mode
+    and the plain bf16 mode).  torch.float32 with a bfloat16 compute dtype: colour maps in, cp1
+    and features out in float32, bf16 only as the DSAM operands; with a float32
+    compute dtype it is the float32 mode.  Anything else is refused."""
+    if interface_dtype is None:
+        return False
+    if interface_dtype != torch.float32:
+        raise ValueError(f"hot_path: interface_dtype {interface_dtype} (None or torch.float32)")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"hot_path: interface_dtype with compute dtype {dtype} (float32 or bfloat16)")
+    return dtype == torch.bfloat16
+
+
+def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_modules=None, interface_dtype=None):
     """Launch the ratio-independent part of the hot path (call it before the ratio predictor,
     pass the result to ``hot_path(..., prepared=)``).  bf16 on the GPU: on the side stream
     (``overlap`` False: on the current stream).  With ``dsam_modules`` (bf16) the filters of the
     PREPACK DSAMs are packed here too, from the parameters as they are now (after the previous
-    optimizer step)."""
+    optimizer step).  ``interface_dtype``: see ``float32_interface``; torch.float32 with bf16 keeps
+    the colour maps float32 (one launch writes colour 0's bf16 NHWC operand and the float32 NHWC
+    residuals of colours 1-3)."""
+    f32io = float32_interface(dtype, interface_dtype)
     pv = pixel_values.detach().float().contiguous()
-    cols = [c.detach().to(dtype).contiguous() for c in colors]
+    cols = [c.detach().to(torch.float32 if f32io else dtype).contiguous() for c in colors]
     bf16 = dtype == torch.bfloat16
     side = _Side(pv.device, bf16 and pv.is_cuda and overlap)
     held = {}
 
     def work():
         held["modes"] = m = ops.edsam_modes(pv)
-        nhwc = ops.nchw_to_nhwc_multi(cols) if bf16 else None
+        if f32io:
+            nhwc = ops.nchw_to_nhwc_multi_f32(cols, [torch.bfloat16] + [torch.float32] * 3)
+        else:
+            nhwc = ops.nchw_to_nhwc_multi(cols) if bf16 else None
         packs = {}
         if bf16 and dsam_modules is not None:
             for k in PREPACK:
@@ -195,7 +220,8 @@ def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_module
         held["packs"] = packs
         return [m.info, m.ws, m.masks, nhwc, [t for pk in packs.values() for t in pk if t is not None]]
     _, _, _, nhwc, _ = side.run(work, pv, *cols)
-    return Prepared(side, pv, held["modes"], cols, nhwc, dtype, _sources(pixel_values, colors), held["packs"])
+    return Prepared(side, pv, held["modes"], cols, nhwc, dtype, _sources(pixel_values, colors), held["packs"],
+                    interface_dtype)
 
 
 class HotPathFunction(torch.autograd.Function):
@@ -203,10 +229,13 @@ class HotPathFunction(torch.autograd.Function):
     def forward(ctx, pixel_values, ratio, cfg, c0, c1, c2, c3, *params):
         dtype = cfg["dtype"]
         prepared = cfg.get("prepared")
+        f32io = float32_interface(dtype, cfg.get("interface_dtype"))
         if prepared is None:
-            prepared = prepare(pixel_values, (c0, c1, c2, c3), dtype)
+            prepared = prepare(pixel_values, (c0, c1, c2, c3), dtype, interface_dtype=cfg.get("interface_dtype"))
         if prepared.dtype != dtype:
             raise ValueError("hot_path: prepared for another compute dtype")
+        if prepared.interface_dtype != cfg.get("interface_dtype"):
+            raise ValueError("hot_path: prepared for another interface dtype")
         colors = prepared.colors
         dsam_p = [params[9 * k:9 * k + 9] for k in range(3)]
         dggm_p = params[27:35]
@@ -266,9 +295,17 @@ class HotPathFunction(torch.autograd.Function):
                                                                           cp1_nhwc=(1, 2)),
                                           *cp1[0:3], *colors[0:3], pixel_values)
                 bias4 = stack4([b.detach() for b in dsam_p[k][1:8:2]])
-                out_nhwc = ops.dsam_fwd_nhwc(x_nhwc[k], codes[k], info, packs[k][0], bias4, residual_nhwc=res_nhwc[k],
-                                             plan=conv_plans[k])
-                cp1.append(out_nhwc)
+                if f32io:
+                    # float32 residual in, cp1[k+1] kept float32 (DGGM and the outputs read it) and
+                    # rounded once for the next DSAM, by the same epilogue
+                    out_nhwc, out_f32 = ops.dsam_fwd_nhwc_f32io(x_nhwc[k], codes[k], info, packs[k][0], bias4,
+                                                                residual_f32_nhwc=res_nhwc[k], want_bf16=(k < 2),
+                                                                plan=conv_plans[k])
+                    cp1.append(out_f32)
+                else:
+                    out_nhwc = ops.dsam_fwd_nhwc(x_nhwc[k], codes[k], info, packs[k][0], bias4,
+                                                 residual_nhwc=res_nhwc[k], plan=conv_plans[k])
+                    cp1.append(out_nhwc)
                 if k < 2:
                     x_nhwc.append(out_nhwc)
             cp1_nhwc = (1, 2, 3)
@@ -298,6 +335,7 @@ class HotPathFunction(torch.autograd.Function):
         ctx.packs = packs
         ctx.save_for_backward(pixel_values, *dggm_p)
         ctx.dtype = dtype
+        ctx.f32io = f32io
         ctx.in_dtypes = [c.dtype for c in (c0, c1, c2, c3)]
         return tuple(outs)
 
@@ -311,7 +349,7 @@ class HotPathFunction(torch.autograd.Function):
                 shape = ctx.x_nhwc[0].shape if k == 0 else None
                 raise RuntimeError("hot-path backward needs gradients for all four backbone features"
                                    if shape is None else "missing gradient for scale 0")
-            G.append(g.to(dtype).contiguous())
+            G.append(g.to(torch.float32 if ctx.f32io else dtype).contiguous())
         bf16 = dtype == torch.bfloat16
         # bf16 on the GPU: the main stream runs dX2 -> dX1 -> dW1 + dW0 (one launch); the DGGM backward
         # and the dW of dsam2 run beside it on the side stream (their persistent kernels take CUs as the
@@ -329,7 +367,12 @@ class HotPathFunction(torch.autograd.Function):
         hook = ctx.cfg.get("grad_hook")
         dcp = G[3]
         # bf16: the three upstream gradients the cascade reads in NHWC, converted by one launch
-        g_nhwc = dict(zip((3, 2, 1), ops.nchw_to_nhwc_multi([G[3], G[2], G[1]]))) if bf16 else {}
+        # (float32 interface: the same launch rounds them, float32 NCHW -> bf16 NHWC; the DGGM
+        # backward takes them in float32)
+        if ctx.f32io:
+            g_nhwc = dict(zip((3, 2, 1), ops.nchw_to_nhwc_multi_f32([G[3], G[2], G[1]], [torch.bfloat16] * 3)))
+        else:
+            g_nhwc = dict(zip((3, 2, 1), ops.nchw_to_nhwc_multi([G[3], G[2], G[1]]))) if bf16 else {}
         dcp_nhwc = g_nhwc[3] if bf16 else ops.nchw_to_nhwc(dcp)
         grads_dsam = [None, None, None]
         def dsam_dw(k, dcp, dcp_nhwc):
@@ -379,7 +422,7 @@ class HotPathFunction(torch.autograd.Function):
 
 
 def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch.float32, check_status=False,
-             grad_hook=None, status_sink=None, prepared=None, overlap=True, overlap_bwd=True):
+             grad_hook=None, status_sink=None, prepared=None, overlap=True, overlap_bwd=True, interface_dtype=None):
     """Run the fused hot path.  ``dsam_modules``: the three DSAModule instances;
     ``dggm_module``: the DepthGradientInjectionResidual instance.  ``check_status`` raises the
     reference's ValueError for a degenerate depth histogram right away (synchronising);
@@ -394,7 +437,13 @@ def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch
     data-parallel step overlaps its gradient all-reduces there instead: graph_guard's two branches).
     ``overlap`` False keeps every launch on the current stream (no side stream of the hot path's
     own: a caller that runs other work beside it on a stream of its own, e.g. the next batch's
-    ratio predictor, stays within two concurrent branches when captured)."""
+    ratio predictor, stays within two concurrent branches when captured).
+    ``interface_dtype``: None = colour maps, cp1 and features in ``dtype``; torch.float32 with
+    ``dtype=torch.bfloat16`` = the float32-interface mode (colour maps read, cp1 kept and features
+    returned in float32, gradients taken in float32; bf16 only as the DSAM operands: DESIGN.md
+    §5.11); torch.float32 with ``dtype=torch.float32`` is the float32 mode.  Anything else raises
+    ValueError.  A ``prepared`` must have been built with the same value."""
+    float32_interface(dtype, interface_dtype)
     params = []
     for m in dsam_modules:
         for i in range(4):
@@ -405,7 +454,7 @@ def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch
         params += [conv.weight, conv.bias]
     cfg = {"dtype": dtype, "check_status": check_status, "grad_hook": grad_hook, "status_sink": status_sink,
            "pack_cache": [m._pack_cache for m in dsam_modules], "overlap": overlap, "overlap_bwd": overlap_bwd,
-           "prepared": prepared}
+           "prepared": prepared, "interface_dtype": interface_dtype}
     if prepared is not None:
         prepared.check(pixel_values, colors)
     pv = prepared.pixel_values if prepared is not None else pixel_values.detach().float().contiguous()

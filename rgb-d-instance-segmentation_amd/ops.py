@@ -486,6 +486,33 @@ def nchw_to_nhwc_multi(xs):
     return ys
 
 
+class _NhwcJobF32(ctypes.Structure):  # rgbd_nhwc_job_f32
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("B", ctypes.c_int), ("C", ctypes.c_int),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("dst_dtype", ctypes.c_int)]
+
+
+def nchw_to_nhwc_multi_f32(xs, out_dtypes):
+    """Up to four float32 NCHW tensors -> their NHWC copies in one launch
+    (rgbd_nchw_to_nhwc_multi_f32), each as ``out_dtypes[i]``: torch.bfloat16 (one round to nearest
+    even, bitwise ``x.to(bfloat16)``) or torch.float32 (a bitwise copy)."""
+    if not 1 <= len(xs) <= 4 or len(out_dtypes) != len(xs):
+        raise ValueError("nchw_to_nhwc_multi_f32: one to four tensors, one output dtype each")
+    _need_cuda(*xs)
+    arr = (_NhwcJobF32 * len(xs))()
+    ys = []
+    for i, (x, dt) in enumerate(zip(xs, out_dtypes)):
+        if x.dtype != torch.float32 or x.dim() != 4:
+            raise ValueError("nchw_to_nhwc_multi_f32: float32 [B,C,H,W] tensors")
+        if dt not in (torch.bfloat16, torch.float32):
+            raise ValueError("nchw_to_nhwc_multi_f32: output dtypes are bfloat16 or float32")
+        B, C, H, W = x.shape
+        y = torch.empty((B, H, W, C), dtype=dt, device=x.device)
+        arr[i] = _NhwcJobF32(x.data_ptr(), y.data_ptr(), B, C, H, W, _dtype_code(y))
+        ys.append(y)
+    check(_lib.lib().rgbd_nchw_to_nhwc_multi_f32(len(xs), arr, _stream(xs[0].device)), "rgbd_nchw_to_nhwc_multi_f32")
+    return ys
+
+
 def dsam_code_masks(codes):
     """codes: list of uint8 region-code maps -> uint32 device tensor [len(codes)], bit k set when
     code k occurs in map i (the codes the bf16 packed filters are needed for)."""
@@ -604,6 +631,43 @@ def dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, residual_nhwc=None, plan=None
     check(L.rgbd_dsam_fwd_nhwc(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
                                _p(residual_nhwc), _p(out), _p(ws), _stream(x_nhwc.device)), "rgbd_dsam_fwd_nhwc")
     return out
+
+
+def dsam_fwd_nhwc_f32io(x_nhwc, code, info, wfwd, bias4, residual_f32_nhwc=None, want_bf16=True, want_f32=True,
+                        plan=None):
+    """dsam_fwd_nhwc with a float32 interface (rgbd_dsam_fwd_nhwc_f32io[_planned]): bf16 operands,
+    an optional float32 NHWC residual, -> (out_bf16, out_f32), both [B,ho,wo,Co]: out_f32 =
+    residual + (acc + bias) in float32, out_bf16 its one rounding; ``want_bf16`` / ``want_f32``
+    False leave that one out (None)."""
+    _need_cuda(x_nhwc, code, info, wfwd, bias4, residual_f32_nhwc, plan)
+    if x_nhwc.dtype != torch.bfloat16:
+        raise TypeError("dsam_fwd_nhwc_f32io computes in bfloat16 (x_nhwc must be bfloat16)")
+    if not (want_bf16 or want_f32):
+        raise ValueError("dsam_fwd_nhwc_f32io: at least one output")
+    B, h, w, Ci = x_nhwc.shape
+    Co = bias4.shape[-1]
+    ho, wo = (h + 1) // 2, (w + 1) // 2
+    if tuple(code.shape) != (B, h, w):
+        raise ValueError(f"region code {tuple(code.shape)} does not match features {(B, h, w)}")
+    if residual_f32_nhwc is not None and (tuple(residual_f32_nhwc.shape) != (B, ho, wo, Co)
+                                          or residual_f32_nhwc.dtype != torch.float32):
+        raise ValueError(f"residual {tuple(residual_f32_nhwc.shape)} {residual_f32_nhwc.dtype} != float32 "
+                         f"{(B, ho, wo, Co)}")
+    out = torch.empty((B, ho, wo, Co), dtype=torch.bfloat16, device=x_nhwc.device) if want_bf16 else None
+    out32 = torch.empty((B, ho, wo, Co), dtype=torch.float32, device=x_nhwc.device) if want_f32 else None
+    b4 = bias4.detach().float().contiguous()
+    L = _lib.lib()
+    if plan is not None:
+        ws = _workspace(x_nhwc.device, L.rgbd_dsam_run_workspace_size(LEG_FWD, B, Ci, h, w, Co), "dsam_conv")
+        check(L.rgbd_dsam_fwd_nhwc_f32io_planned(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd),
+                                                 _p(b4), None, _p(out), _p(plan), _p(ws), _stream(x_nhwc.device),
+                                                 _p(residual_f32_nhwc), _p(out32)), "rgbd_dsam_fwd_nhwc_f32io_planned")
+        return out, out32
+    ws = _workspace(x_nhwc.device, L.rgbd_dsam_conv_workspace_size(RGBD_BF16, B, Ci, h, w, Co), "dsam_conv")
+    check(L.rgbd_dsam_fwd_nhwc_f32io(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
+                                     None, _p(out), _p(ws), _stream(x_nhwc.device), _p(residual_f32_nhwc),
+                                     _p(out32)), "rgbd_dsam_fwd_nhwc_f32io")
+    return out, out32
 
 
 def dsam_bwd_data(gout_nhwc, code, wbwd, gin_nchw, want_nhwc=False, cin=None, gin_nhwc=None, want_nchw=True,

@@ -22,9 +22,10 @@ from .hot_path import hot_path, prepare
 
 class StreamingHotPath:
     def __init__(self, ratio_predictor, dsams, dggm, H, W, B=1, dtype=torch.bfloat16, device="cuda",
-                 color_channels=(96, 192, 384, 768)):
+                 color_channels=(96, 192, 384, 768), interface_dtype=None):
         self.rp, self.dsams, self.dg = ratio_predictor, list(dsams), dggm
         self.dtype = dtype
+        self.interface_dtype = interface_dtype  # hot_path.float32_interface; the static colour buffers follow it
         for m in [self.rp, self.dg] + self.dsams:
             m.compute_dtype = dtype
             m.eval()
@@ -34,16 +35,18 @@ class StreamingHotPath:
         h, w = -(-H // 4), -(-W // 4)
         self.colors = []
         for c in color_channels:
-            self.colors.append(torch.zeros((B, c, h, w), dtype=dtype, device=dev))
+            self.colors.append(torch.zeros((B, c, h, w), dtype=interface_dtype or dtype, device=dev))
             h, w = -(-h // 2), -(-w // 2)
         self.graph = None
         self.outs = None
 
     def _run(self):
         pv = ops.assemble_pixel_values(self.depth_u8, self.rgb_u8)
-        prep = prepare(pv, self.colors, self.dtype, dsam_modules=self.dsams)  # beside the ratio predictor
+        prep = prepare(pv, self.colors, self.dtype, dsam_modules=self.dsams,  # beside the ratio predictor
+                       interface_dtype=self.interface_dtype)
         ratio = self.rp(pv[:, 3:6])
-        return hot_path(pv, ratio, self.colors, self.dsams, self.dg, dtype=self.dtype, prepared=prep), ratio
+        return hot_path(pv, ratio, self.colors, self.dsams, self.dg, dtype=self.dtype, prepared=prep,
+                        interface_dtype=self.interface_dtype), ratio
 
     def capture(self):
         """Warm up (packs weights, sizes workspaces) on a side stream, then capture the path."""
