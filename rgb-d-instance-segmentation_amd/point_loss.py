@@ -250,7 +250,7 @@ class _MatchedRows(torch.autograd.Function):
     def backward(ctx, g):
         (flat,) = ctx.saved_tensors
         shape = ctx.shape
-        gx = g.new_zeros((shape[0] * shape[1], *shape[2:]))
+        gx = torch.zeros((shape[0] * shape[1], *shape[2:]), dtype=g.dtype, device=g.device)
         gx.index_copy_(0, flat, g)
         return gx.view(shape), None
 
