@@ -419,6 +419,17 @@ int rgbd_point_sample_sets(int dtype, const void* maps, int nmaps, int h, int w,
                            const int* set_of_map, int P, float* out, void* stream);
 int rgbd_point_sample_bwd(const float* gout, int nmaps, int h, int w, const float* coords, int maps_per_coord,
                           int P, float* gmaps, void* stream);
+/* rgbd_point_sample_bwd without float atomics (rgbd_amd.determinism): _emit writes one record
+ * per tap i = (m P + p) 4 + e — keys[i] = the flat index m h w + y w + x of the tap's cell in gmaps
+ * (int32; the sentinel nmaps h w for a tap outside the map or a zero gout), coef[i] = gout[m][p] *
+ * tap weight; keys and coef hold nmaps P 4 elements, 16-byte aligned.  The caller sorts the keys
+ * stably carrying i; rgbd_ordered_gather then OVERWRITES out[cell], cell < ncells, with the sum of
+ * coef[sorted_idx[j]] over the cell's segment of sorted_keys in ascending j, in the chunked order
+ * of rgbd_msda_bwd_gather (+0 for an empty segment). */
+int rgbd_point_sample_bwd_emit(const float* gout, int nmaps, int h, int w, const float* coords, int maps_per_coord,
+                               int P, int* keys, float* coef, void* stream);
+int rgbd_ordered_gather(const int* sorted_keys, const long long* sorted_idx, const float* coef, long long ntaps,
+                        long long ncells, float* out, void* stream);
 int rgbd_match_cost(const float* pred, int B, int Q, int P, const float* tgt, const int* toff,
                     const float* class_cost, const long long* coff, float w_mask, float w_class, float w_dice,
                     float* cost, void* stream);
@@ -466,6 +477,22 @@ int rgbd_msda_fwd(int dtype, const void* value, int B, int L, const int* shapes_
 int rgbd_msda_bwd(int dtype, const void* value, int B, int L, const int* shapes_host, int NH, int D, int Q,
                   int P, const float* loc, const float* attw, const void* gout, float* gvalue, float* gloc,
                   float* gattw, void* stream);
+/* The same backward without float atomics (rgbd_amd.determinism), in three stages.
+ * rgbd_msda_bwd_emit writes gloc and gattw exactly as rgbd_msda_bwd does (bitwise) and, instead
+ * of scattering, one record per tap i = ((((b NH + h) Q + q) L + l) P + p) 4 + e:
+ * keys[i] = (b NH + h) S + cell (int32; the sentinel B NH S for a zero-padding tap) and
+ * coef[i] = attw * bilinear tap weight; keys and coef hold B NH Q L P 4 elements.  The caller
+ * sorts the keys stably, carrying i (sorted_keys int32, sorted_idx int64, ascending i within a
+ * key).  rgbd_msda_bwd_gather then writes EVERY row of gvalue (no zeroing needed; +0 for a row no
+ * tap reaches): gvalue[b][s][h][c] = sum of coef[i] * gout[b][q(i)][h][c] over the key's segment
+ * in ascending i, in chunks of 256 taps cut at fixed offsets from the segment's start — each chunk
+ * summed in order from +0, the chunk sums added in chunk order from +0 (float32, no FMA).  LP = L * P.
+ * Both need B NH S and the tap count below 2^31 - 1 (RGBD_E_SHAPE otherwise). */
+int rgbd_msda_bwd_emit(int dtype, const void* value, int B, int L, const int* shapes_host, int NH, int D, int Q,
+                       int P, const float* loc, const float* attw, const void* gout, int* keys, float* coef,
+                       float* gloc, float* gattw, void* stream);
+int rgbd_msda_bwd_gather(int dtype, const int* sorted_keys, const long long* sorted_idx, const float* coef,
+                         const void* gout, int B, int S, int NH, int D, int Q, int LP, float* gvalue, void* stream);
 
 /* The sampling locations of two-coordinate reference points (:990-994) in one pass:
  *   loc[b][q][h][l][p][c] = ref[b][q][l][c] + off[b][q][h][l][p][c] / norm[l][c]

@@ -91,6 +91,8 @@ SIGNATURES = {
     "rgbd_topk_rows_max_n": (_SZ, []),
     "rgbd_topk_rows": (_I, [_P, _I, _I, _I, _P, _P]),
     "rgbd_point_sample_bwd": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    "rgbd_point_sample_bwd_emit": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "rgbd_ordered_gather": (_I, [_P, _P, _P, _LL, _LL, _P, _P]),
     "rgbd_match_cost": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
     "rgbd_match_cost_probs": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, ctypes.c_float, ctypes.c_float,
                                    ctypes.c_float, _P, _P]),
@@ -98,6 +100,8 @@ SIGNATURES = {
     "rgbd_point_losses_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "rgbd_msda_fwd": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rgbd_msda_bwd": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_msda_bwd_emit": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_msda_bwd_gather": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "rgbd_level_memory_workspace_size": (_SZ, [_I, _I, _I]),
     "rgbd_level_memory_fwd": (_I, [_I, _P, _P, _I, _I, _I, _P, _P]),
     "rgbd_level_memory_bwd": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),

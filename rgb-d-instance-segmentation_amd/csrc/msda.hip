@@ -16,9 +16,12 @@
 // gradient) and go . d sample / d(ix, iy) (sampling-location gradient) with shuffles, and
 // scatters weight * tap weight * go into the value gradient with float atomics (as
 // grid_sample's backward does).  Bound: the atomic byte rate.
+// Deterministic mode (k_msda_emit + a stable sort + k_msda_gather, further down): the same value
+// gradient without atomics, summed per destination row in an order fixed by the inputs.
 #include <algorithm>
 
 #include "common.hpp"
+#include "ordered_gather.hpp"
 
 namespace rgbd {
 namespace {
@@ -369,6 +372,121 @@ int launch_bwd(const void* value, const MsdaLevels& lv, int B, int S, int Q, int
   return RGBD_OK;
 }
 
+// ---- deterministic value gradient (rgbd_amd.determinism): no float atomics -------------------
+// Stage 1, k_msda_emit: k_msda_bwd's pass with the scatter replaced by one record per tap.  gloc
+// and gattw come from the same msda_tap, products, shuffles and stores as k_msda_bwd /
+// k_msda_bwd_runs, so they are bitwise the default path's.  Tap
+//   i = ((((b NH + h) Q + q) L + l) P + p) 4 + e      (e: x0y0, x1y0, x0y1, x1y1)
+// gets key[i] = (b NH + h) S + cell (cell = level start + y W + x), or the sentinel B NH S for a
+// padding tap, and coef[i] = attw * w_tap (one float32 product).  The taps of one (image, head)
+// are contiguous and ordered by (q, l, p, e).
+// Stage 2 (the wrapper): a stable sort of the keys carrying i.
+// Stage 3, k_msda_gather: one group of D lanes per destination row (b, s, h), lane = channel.
+// The group finds its key's segment in the sorted keys and sums the terms
+//   coef[i] * go[b][q(i)][h][c]      (one float32 product each, go widened from the value's dtype)
+// over it in ascending i, in the chunked order ordered_gather.hpp defines (chunks of ORDERED_CH =
+// 256 taps at fixed offsets from the segment's start, each summed in order from +0, the partials
+// added in chunk order from +0; one group sums all chunks of its row).  It writes every row of
+// gvalue, exactly +0 for a row no tap reaches: no memset.  Groups are numbered in key order
+// ((b, h, s): neighbouring groups read neighbouring segments and share go rows).
+template <typename T, int D>
+__global__ __launch_bounds__(256) void k_msda_emit(const T* __restrict__ value, MsdaLevels lv, int S, int Q, int NH,
+                                                   int P, const float* __restrict__ loc,
+                                                   const float* __restrict__ attw, const T* __restrict__ gout,
+                                                   long long nqh, int sentinel, int* __restrict__ keys,
+                                                   float* __restrict__ coef, float* __restrict__ gloc,
+                                                   float* __restrict__ gattw) {
+  const int c = threadIdx.x % D;
+  const long long qh = (long long)blockIdx.x * (256 / D) + threadIdx.x / D;
+  // every lane of a group takes part in the shuffles: out-of-range groups run with zero weight
+  const bool live = qh < nqh;
+  const long long q0 = live ? qh : 0;
+  const int h = (int)(q0 % NH);
+  const long long bq = q0 / NH;
+  const long long b = bq / Q;
+  const int q = (int)(bq % Q);
+  const float* lq = loc + q0 * lv.L * P * 2;
+  const float* wq = attw + q0 * lv.L * P;
+  const T* vb = value + b * S * NH * D + (long long)h * D + c;
+  const int kbase = (int)(b * NH + h) * S;                                // host: B NH S < 2^31
+  const int ibase = (int)(((b * NH + h) * Q + q) * lv.L * P * 4);         // host: taps < 2^31
+  const float go = live ? Num<T>::to_f(gout[q0 * D + c]) : 0.f;
+  for (int l = 0; l < lv.L; ++l) {
+    const int H = lv.H[l], W = lv.W[l];
+    const long long lo = (long long)lv.start[l] * NH * D;
+    for (int p = 0; p < P; ++p) {
+      const int k = l * P + p;
+      const Tap t = msda_tap(lq[2 * k], lq[2 * k + 1], H, W);
+      const float a = wq[k];
+      float v[4];  // unconditional loads (padding taps read cell 0, then count as zero)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = Num<T>::to_f(vb[lo + (long long)max(t.idx[e], 0) * NH * D]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = t.idx[e] >= 0 ? v[e] : 0.f;
+      const float s = t.w[0] * v[0] + t.w[1] * v[1] + t.w[2] * v[2] + t.w[3] * v[3];
+      // d sample / d ix, d iy (zero-padded taps are zeros)
+      const float dsx = (1.f - t.ly) * (v[1] - v[0]) + t.ly * (v[3] - v[2]);
+      const float dsy = (1.f - t.lx) * (v[2] - v[0]) + t.lx * (v[3] - v[1]);
+      const float gw = group_sum<D>(go * s);
+      const float gx = group_sum<D>(go * dsx);
+      const float gy = group_sum<D>(go * dsy);
+      if (live) {
+        if (c == 0) {
+          gattw[q0 * lv.L * P + k] = gw;
+          gloc[(q0 * lv.L * P + k) * 2] = a * gx * (float)W;
+          gloc[(q0 * lv.L * P + k) * 2 + 1] = a * gy * (float)H;
+        }
+        if (c < 4) {  // lane e of the group writes tap e's record
+          const int idx = c == 0 ? t.idx[0] : c == 1 ? t.idx[1] : c == 2 ? t.idx[2] : t.idx[3];
+          const float w = c == 0 ? t.w[0] : c == 1 ? t.w[1] : c == 2 ? t.w[2] : t.w[3];
+          keys[ibase + k * 4 + c] = idx >= 0 ? kbase + lv.start[l] + idx : sentinel;
+          coef[ibase + k * 4 + c] = a * w;
+        }
+      }
+    }
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void k_msda_gather(const int* __restrict__ skeys, const long long* __restrict__ sidx,
+                                                     int ntaps, const float* __restrict__ coef,
+                                                     const T* __restrict__ gout, int nrows, int S, int Q, int NH,
+                                                     int LP4, float* __restrict__ gvalue) {
+  const int c = threadIdx.x % D;
+  const long long g = (long long)blockIdx.x * (256 / D) + threadIdx.x / D;  // = the row's key
+  if (g >= nrows) return;
+  const int key = (int)g;
+  const int bh = key / S, s = key - bh * S;
+  const int b = bh / NH, h = bh - b * NH;
+  const int lo = seg_lower_bound(skeys, 0, ntaps, key);
+  const int hi = seg_lower_bound(skeys, lo, ntaps, key + 1);
+  const T* gb = gout + ((long long)b * Q * NH + h) * D + c;
+  const float sum = ordered_segment_sum<ORDERED_CH>(lo, hi, [&](int j) {
+    const int i = (int)sidx[j];
+    const int q = i / LP4 - bh * Q;
+    return coef[i] * Num<T>::to_f(gb[(long long)q * NH * D]);
+  });
+  gvalue[(((long long)b * S + s) * NH + h) * D + c] = sum;
+}
+
+template <typename T, int D>
+void launch_emit(const void* value, const MsdaLevels& lv, int B, int S, int Q, int NH, int P, const float* loc,
+                 const float* attw, const void* gout, int* keys, float* coef, float* gloc, float* gattw,
+                 hipStream_t s) {
+  const long long nqh = (long long)B * Q * NH;
+  k_msda_emit<T, D><<<(unsigned)ceil_div(nqh, 256 / D), 256, 0, s>>>((const T*)value, lv, S, Q, NH, P, loc, attw,
+                                                                    (const T*)gout, nqh, B * NH * S, keys, coef, gloc,
+                                                                    gattw);
+}
+
+template <typename T, int D>
+void launch_gather(const int* skeys, const long long* sidx, int ntaps, const float* coef, const void* gout, int B,
+                   int S, int Q, int NH, int LP, float* gvalue, hipStream_t s) {
+  const int nrows = B * S * NH;
+  k_msda_gather<T, D><<<(unsigned)ceil_div(nrows, 256 / D), 256, 0, s>>>(skeys, sidx, ntaps, coef, (const T*)gout,
+                                                                        nrows, S, Q, NH, LP * 4, gvalue);
+}
+
 // Sampling locations of the two-coordinate reference points (:990-994):
 //   loc[b][q][h][l][p][c] = ref[b][q][l][c] + (off[b][q][h][l][p][c] / norm[l][c])
 // with the division in the offsets' dtype (torch: bf16 / int64 -> bf16, computed in float and
@@ -453,6 +571,60 @@ extern "C" int rgbd_msda_bwd(int dtype, const void* value, int B, int L, const i
     else r = launch_bwd<bf16_t, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
   }
   if (r != RGBD_OK) return r;
+  RGBD_CHECK_LAUNCH();
+  return RGBD_OK;
+}
+
+extern "C" int rgbd_msda_bwd_emit(int dtype, const void* value, int B, int L, const int* shapes_host, int NH, int D,
+                                  int Q, int P, const float* loc, const float* attw, const void* gout, int* keys,
+                                  float* coef, float* gloc, float* gattw, void* stream) {
+  RGBD_REQUIRE(value && loc && attw && gout && keys && coef && gloc && gattw && B > 0 && NH > 0 && Q > 0 && P > 0,
+               RGBD_E_ARG);
+  RGBD_REQUIRE(D == 16 || D == 32 || D == 64, RGBD_E_SHAPE);
+  RGBD_REQUIRE(dtype == RGBD_F32 || dtype == RGBD_BF16, RGBD_E_DTYPE);
+  RGBD_REQUIRE(((uintptr_t)value & 15) == 0 && ((uintptr_t)gout & 15) == 0, RGBD_E_SHAPE);
+  MsdaLevels lv;
+  int S = 0;
+  const int rc = msda_levels(L, shapes_host, lv, S);
+  if (rc) return rc;
+  // int32 keys (the sentinel B NH S included) and int32 tap indices
+  RGBD_REQUIRE((long long)B * NH * S <= 0x7ffffffell, RGBD_E_SHAPE);
+  RGBD_REQUIRE((long long)B * NH * Q * L * P * 4 <= 0x7ffffffell, RGBD_E_SHAPE);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == RGBD_F32) {
+    if (D == 32) launch_emit<float, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+    else if (D == 64) launch_emit<float, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+    else launch_emit<float, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+  } else {
+    if (D == 32) launch_emit<bf16_t, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+    else if (D == 64) launch_emit<bf16_t, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+    else launch_emit<bf16_t, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
+  }
+  RGBD_CHECK_LAUNCH();
+  return RGBD_OK;
+}
+
+extern "C" int rgbd_msda_bwd_gather(int dtype, const int* sorted_keys, const long long* sorted_idx, const float* coef,
+                                    const void* gout, int B, int S, int NH, int D, int Q, int LP, float* gvalue,
+                                    void* stream) {
+  RGBD_REQUIRE(sorted_keys && sorted_idx && coef && gout && gvalue && B > 0 && S > 0 && NH > 0 && Q > 0 && LP > 0,
+               RGBD_E_ARG);
+  RGBD_REQUIRE(D == 16 || D == 32 || D == 64, RGBD_E_SHAPE);
+  RGBD_REQUIRE(dtype == RGBD_F32 || dtype == RGBD_BF16, RGBD_E_DTYPE);
+  RGBD_REQUIRE((long long)B * NH * S <= 0x7ffffffell, RGBD_E_SHAPE);
+  const long long ntaps = (long long)B * NH * Q * LP * 4;
+  RGBD_REQUIRE(ntaps <= 0x7ffffffell, RGBD_E_SHAPE);
+  hipStream_t s = (hipStream_t)stream;
+  const int n = (int)ntaps;
+  if (dtype == RGBD_F32) {
+    if (D == 32) launch_gather<float, 32>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+    else if (D == 64) launch_gather<float, 64>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+    else launch_gather<float, 16>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+  } else {
+    if (D == 32) launch_gather<bf16_t, 32>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+    else if (D == 64) launch_gather<bf16_t, 64>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+    else launch_gather<bf16_t, 16>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
+  }
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }

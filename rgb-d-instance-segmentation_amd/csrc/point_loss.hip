@@ -14,7 +14,10 @@
 //                       grid_sampler formula and tap order
 //   k_point_sample_bwd  the transposed scatter (f32 atomics into the map gradient, as ATen's
 //                       grid_sampler_2d_backward does)
-//   k_match_cost        one workgroup per (image, query): per point the positive / negative BCE
+//   k_point_sample_emit / k_ordered_gather  the same scatter without atomics (deterministic
+//                       mode): one (cell, contribution) record per tap, sorted by the wrapper,
+//                       then one fixed-order sum per cell
+//   k_match_cost       one workgroup per (image, query): per point the positive / negative BCE
 //                       and the sigmoid of the query's logit, reduced against every target's
 //                       labels in one pass over the points (T targets in registers per chunk)
 //   k_point_losses      one workgroup per matched pair: BCE mean and the dice term of the row;
@@ -22,6 +25,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "ordered_gather.hpp"
 
 using namespace rgbd;
 
@@ -96,6 +100,43 @@ __global__ __launch_bounds__(256) void k_point_sample_bwd(const float* __restric
   if (in(t.y0, t.x0 + 1)) atomicAdd(mp + t.y0 * w + t.x0 + 1, g * t.ne);
   if (in(t.y0 + 1, t.x0)) atomicAdd(mp + (t.y0 + 1) * w + t.x0, g * t.sw);
   if (in(t.y0 + 1, t.x0 + 1)) atomicAdd(mp + (t.y0 + 1) * w + t.x0 + 1, g * t.se);
+}
+
+// Deterministic form of k_point_sample_bwd (rgbd_amd.determinism), the three stages of
+// ordered_gather.hpp.  k_point_sample_emit: tap i = (m P + p) 4 + e (e: nw, ne, sw, se) gets
+// key[i] = m h w + y w + x, the flat index of its cell in gmaps — or the sentinel nmaps h w for a
+// tap outside the map or a zero gout (k_point_sample_bwd skips those too) — and
+// coef[i] = gout[m][p] * w_tap, the product k_point_sample_bwd adds.  After the wrapper's stable
+// sort of the keys, k_ordered_gather gives every cell one thread, which sums coef over the cell's
+// segment in ascending i, in the chunked order of ordered_gather.hpp, and writes every cell
+// (+0 for an empty one).
+__global__ __launch_bounds__(256) void k_point_sample_emit(const float* __restrict__ gout, int nmaps, int h, int w,
+                                                           const float* __restrict__ coords, int per, int P,
+                                                           int* __restrict__ keys, float* __restrict__ coef) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= (long long)nmaps * P) return;
+  const int m = (int)(i / P), p = (int)(i % P);
+  const float g = gout[i];
+  const float2 c = reinterpret_cast<const float2*>(coords)[(long long)(m / per) * P + p];
+  const Taps t = taps(c.x, c.y, h, w);
+  const int sentinel = nmaps * h * w, base = m * h * w;  // host: nmaps h w < 2^31
+  auto key = [&](int y, int x) {
+    return g != 0.f && x >= 0 && x < w && y >= 0 && y < h ? base + y * w + x : sentinel;
+  };
+  reinterpret_cast<int4*>(keys)[i] =
+      make_int4(key(t.y0, t.x0), key(t.y0, t.x0 + 1), key(t.y0 + 1, t.x0), key(t.y0 + 1, t.x0 + 1));
+  reinterpret_cast<float4*>(coef)[i] = make_float4(g * t.nw, g * t.ne, g * t.sw, g * t.se);
+}
+
+__global__ __launch_bounds__(256) void k_ordered_gather(const int* __restrict__ skeys,
+                                                        const long long* __restrict__ sidx, int ntaps,
+                                                        const float* __restrict__ coef, int ncells,
+                                                        float* __restrict__ out) {
+  const long long cell = blockIdx.x * 256ll + threadIdx.x;
+  if (cell >= ncells) return;
+  const int lo = seg_lower_bound(skeys, 0, ntaps, (int)cell);
+  const int hi = seg_lower_bound(skeys, lo, ntaps, (int)cell + 1);
+  out[cell] = ordered_segment_sum<ORDERED_CH>(lo, hi, [&](int j) { return coef[sidx[j]]; });
 }
 
 // BCEWithLogits (ATen binary_cross_entropy_with_logits, no weights): with m = max(-x, 0),
@@ -367,6 +408,33 @@ int rgbd_point_sample_bwd(const float* gout, int nmaps, int h, int w, const floa
   RGBD_REQUIRE(gout && coords && gmaps, RGBD_E_ARG);
   k_point_sample_bwd<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(gout, nmaps, h, w, coords,
                                                                                    maps_per_coord, P, gmaps);
+  RGBD_CHECK_LAUNCH();
+  return RGBD_OK;
+}
+
+int rgbd_point_sample_bwd_emit(const float* gout, int nmaps, int h, int w, const float* coords, int maps_per_coord,
+                               int P, int* keys, float* coef, void* stream) {
+  RGBD_REQUIRE(nmaps >= 0 && h > 0 && w > 0 && P >= 0 && maps_per_coord > 0, RGBD_E_ARG);
+  const long long n = (long long)nmaps * P;
+  if (n == 0) return RGBD_OK;
+  RGBD_REQUIRE(gout && coords && keys && coef, RGBD_E_ARG);
+  RGBD_REQUIRE(((uintptr_t)keys & 15) == 0 && ((uintptr_t)coef & 15) == 0, RGBD_E_SHAPE);  // 16-byte records
+  // int32 keys (the sentinel nmaps h w included) and int32 tap indices
+  RGBD_REQUIRE((long long)nmaps * h * w <= 0x7ffffffell && n * 4 <= 0x7ffffffell, RGBD_E_SHAPE);
+  k_point_sample_emit<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(gout, nmaps, h, w, coords,
+                                                                                    maps_per_coord, P, keys, coef);
+  RGBD_CHECK_LAUNCH();
+  return RGBD_OK;
+}
+
+int rgbd_ordered_gather(const int* sorted_keys, const long long* sorted_idx, const float* coef, long long ntaps,
+                        long long ncells, float* out, void* stream) {
+  RGBD_REQUIRE(ntaps >= 0 && ncells >= 0, RGBD_E_ARG);
+  if (ncells == 0) return RGBD_OK;
+  RGBD_REQUIRE(out && (ntaps == 0 || (sorted_keys && sorted_idx && coef)), RGBD_E_ARG);
+  RGBD_REQUIRE(ntaps <= 0x7ffffffell && ncells <= 0x7ffffffell, RGBD_E_SHAPE);
+  k_ordered_gather<<<(unsigned)((ncells + 255) / 256), 256, 0, (hipStream_t)stream>>>(sorted_keys, sorted_idx,
+                                                                                     (int)ntaps, coef, (int)ncells, out);
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }

@@ -8,15 +8,17 @@ copy of the value, stack, weight and sum.
 
 ``HipMSDeformAttn`` keeps the projections, the softmax and the location arithmetic as the same
 torch calls and replaces the core with ``MSDeformAttnFunction`` (csrc/msda.hip: one fused gather
-kernel forward, one fused backward with atomics for the value gradient).  ``install(model)``
-swaps the class of every HF module in place (parameters / state_dict keys unchanged).
+kernel forward, one fused backward; the value gradient is scattered with float atomics, or, in
+``determinism``'s deterministic mode, emitted, sorted and summed per row in a fixed order).
+``install(model)`` swaps the class of every HF module in place (parameters / state_dict keys
+unchanged).
 """
 import torch
 from torch import nn
 from transformers.models.mask2former.modeling_mask2former import (
     Mask2FormerPixelDecoderEncoderMultiscaleDeformableAttention as _HFMSDA)
 
-from . import _lib, ops
+from . import _lib, determinism, ops
 from ._lib import RGBD_BF16, RGBD_F32, check
 
 _CODE = {torch.float32: RGBD_F32, torch.bfloat16: RGBD_BF16}
@@ -28,12 +30,13 @@ class MSDeformAttnFunction(torch.autograd.Function):
         ctx.shapes = [tuple(int(x) for x in hw) for hw in shapes]
         ctx.save_for_backward(value, loc, attw)
         ctx.loc_dtype, ctx.attw_dtype = loc.dtype, attw.dtype
+        ctx.deterministic = determinism.is_deterministic()  # the backward runs in the forward's mode
         return ops.msda_forward(value, ctx.shapes, loc, attw)
 
     @staticmethod
     def backward(ctx, gout):
         value, loc, attw = ctx.saved_tensors
-        gv, gl, ga = ops.msda_backward(value, ctx.shapes, loc, attw, gout)
+        gv, gl, ga = ops.msda_backward(value, ctx.shapes, loc, attw, gout, deterministic=ctx.deterministic)
         return gv.to(value.dtype), None, gl.to(ctx.loc_dtype), ga.to(ctx.attw_dtype)
 
 

@@ -904,8 +904,10 @@ def msda_forward(value, shapes, loc, attw):
     return out
 
 
-def msda_backward(value, shapes, loc, attw, gout):
-    """-> (grad_value float32 [B,S,NH,D], grad_loc, grad_attw)."""
+def msda_backward(value, shapes, loc, attw, gout, deterministic=False):
+    """-> (grad_value float32 [B,S,NH,D], grad_loc, grad_attw).  ``deterministic``: the value
+    gradient without float atomics (emit, stable sort, ordered gather: csrc/msda.hip), bitwise
+    reproducible; grad_loc and grad_attw are the same bits in both modes."""
     value = value.contiguous()
     loc = loc.float().contiguous()
     attw = attw.float().contiguous()
@@ -914,6 +916,85 @@ def msda_backward(value, shapes, loc, attw, gout):
     gv = torch.empty((B, S, NH, D), dtype=torch.float32, device=value.device)
     gl = torch.empty_like(loc)
     ga = torch.empty_like(attw)
+    if deterministic:
+        gout = gout.view(B, Q, NH * D)
+        per = _msda_det_group(B, S, NH, Q, L, P)
+        for b0 in range(0, B, per):  # whole images: b is the outermost key, so no sum changes
+            b1 = min(B, b0 + per)
+            keys, coef = _msda_emit(value[b0:b1], arr, loc[b0:b1], attw[b0:b1], gout[b0:b1], gl[b0:b1], ga[b0:b1])
+            skeys, sidx = ordered_sort(keys)
+            _msda_gather(skeys, sidx, coef, gout[b0:b1], Q, L * P, gv[b0:b1])
+        return gv, gl, ga
     check(_lib.lib().rgbd_msda_bwd(_dtype_code(value), _p(value), B, L, arr, NH, D, Q, P, _p(loc), _p(attw),
                                    _p(gout), _p(gv), _p(gl), _p(ga), _stream(value.device)), "rgbd_msda_bwd")
     return gv, gl, ga
+
+
+# ---- deterministic scatters: emit -> stable sort -> ordered gather (csrc/ordered_gather.hpp)
+# the taps of one deterministic MSDA launch group (per tap 8 bytes of records, 12 of sort output
+# and torch.sort's temporaries: ~40 bytes measured); a larger batch runs in groups of whole images
+MSDA_DET_MAX_TAPS = 1 << 27
+_INT32_LIMIT = (1 << 31) - 2
+
+
+def _msda_det_group(B, S, NH, Q, L, P):
+    """Images per deterministic launch group."""
+    taps = NH * Q * L * P * 4
+    if taps > _INT32_LIMIT or NH * S > _INT32_LIMIT:
+        raise ValueError(f"msda (deterministic): {taps} taps / {NH * S} value rows in one image exceed the int32 "
+                         "keys of the ordered gather")
+    return max(1, min(B, MSDA_DET_MAX_TAPS // taps, _INT32_LIMIT // taps, _INT32_LIMIT // (NH * S)))
+
+
+def _msda_emit(value, arr, loc, attw, gout, gl, ga):
+    """Stage 1 on contiguous (batch-sliced) tensors: writes gl / ga, returns (keys int32, coef
+    float32), one element per tap ((b, h, q, l, p, e) order)."""
+    B, S, NH, D = value.shape
+    _, Q, _, L, P, _ = loc.shape
+    n = B * NH * Q * L * P * 4
+    keys = torch.empty((n,), dtype=torch.int32, device=value.device)
+    coef = torch.empty((n,), dtype=torch.float32, device=value.device)
+    check(_lib.lib().rgbd_msda_bwd_emit(_dtype_code(value), _p(value), B, L, arr, NH, D, Q, P, _p(loc), _p(attw),
+                                        _p(gout), _p(keys), _p(coef), _p(gl), _p(ga), _stream(value.device)),
+          "rgbd_msda_bwd_emit")
+    return keys, coef
+
+
+def ordered_sort(keys):
+    """Stage 2: the keys sorted stably -> (sorted keys int32, tap index int64); equal keys keep
+    ascending tap index.  No host synchronisation."""
+    return torch.sort(keys, stable=True)
+
+
+def _msda_gather(skeys, sidx, coef, gout, Q, LP, gv):
+    B, S, NH, D = gv.shape
+    check(_lib.lib().rgbd_msda_bwd_gather(_dtype_code(gout), _p(skeys), _p(sidx), _p(coef), _p(gout), B, S, NH, D, Q,
+                                          LP, _p(gv), _stream(gv.device)), "rgbd_msda_bwd_gather")
+
+
+def msda_backward_stages(value, shapes, loc, attw, gout):
+    """The deterministic backward of one launch group with its intermediates, for tests and
+    tools: -> dict(keys, coef, sorted_keys, sorted_idx, gv, gl, ga).  tests/checkers/
+    ordered_scatter.py restates gv from the other entries."""
+    value = value.contiguous()
+    loc = loc.float().contiguous()
+    attw = attw.float().contiguous()
+    B, S, NH, D, Q, L, P, arr = _msda_args(value, shapes, loc, attw)
+    gout = gout.to(value.dtype).contiguous().view(B, Q, NH * D)
+    if _msda_det_group(B, S, NH, Q, L, P) < B:
+        raise ValueError("msda_backward_stages: the batch does not fit one launch group")
+    gv = torch.empty((B, S, NH, D), dtype=torch.float32, device=value.device)
+    gl = torch.empty_like(loc)
+    ga = torch.empty_like(attw)
+    keys, coef = _msda_emit(value, arr, loc, attw, gout, gl, ga)
+    skeys, sidx = ordered_sort(keys)
+    _msda_gather(skeys, sidx, coef, gout, Q, L * P, gv)
+    return dict(keys=keys, coef=coef, sorted_keys=skeys, sorted_idx=sidx, gv=gv, gl=gl, ga=ga)
+
+
+def ordered_gather(skeys, sidx, coef, out):
+    """out.view(-1)[cell] = the ordered sum of coef[sidx[j]] over cell's segment of skeys (every
+    cell written, +0 for an empty segment)."""
+    check(_lib.lib().rgbd_ordered_gather(_p(skeys), _p(sidx), _p(coef), skeys.numel(), out.numel(), _p(out),
+                                         _stream(out.device)), "rgbd_ordered_gather")
+    return out

@@ -20,9 +20,9 @@ import torch
 from torch import nn
 from transformers.models.mask2former.modeling_mask2former import Mask2FormerHungarianMatcher, Mask2FormerLoss
 
-from . import _lib
+from . import _lib, determinism
 from ._lib import RGBD_BF16, RGBD_F32, check
-from .ops import LsaResult, _need_cuda, _p, _stream, device_const, device_vec
+from .ops import LsaResult, _need_cuda, _p, _stream, device_const, device_vec, ordered_gather, ordered_sort
 
 # loss_masks' uncertainty top-k: unsorted by default (the loss terms are sums over the point set,
 # so only the float summation order changes; the segmented sort cost ~2.4 ms per whole-model
@@ -114,11 +114,34 @@ def _sample(maps, coords):
     return out
 
 
+def point_sample_backward_stages(g, coords, h, w):
+    """The map gradient of ``point_sample`` without float atomics (deterministic mode): one
+    (cell, gout * tap weight) record per tap, a stable sort of the cells, one fixed-order sum per
+    cell (csrc/ordered_gather.hpp).  g float32 [N, P], coords [G, P, 2] -> dict(keys, coef,
+    sorted_keys, sorted_idx, gmaps); every cell of gmaps is written."""
+    g = g.float().contiguous()
+    c = coords.detach().float().contiguous()
+    _need_cuda(g, c)
+    N, P = g.shape
+    if N * h * w > (1 << 31) - 2 or N * P * 4 > (1 << 31) - 2:
+        raise ValueError(f"point_sample (deterministic): {N} maps of {h}x{w} with {P} points exceed the int32 keys "
+                         "of the ordered gather")
+    keys = torch.empty((N * P * 4,), dtype=torch.int32, device=g.device)
+    coef = torch.empty((N * P * 4,), dtype=torch.float32, device=g.device)
+    gmaps = torch.empty((N, h, w), dtype=torch.float32, device=g.device)
+    check(_lib.lib().rgbd_point_sample_bwd_emit(_p(g), N, h, w, _p(c), N // c.shape[0], P, _p(keys), _p(coef),
+                                                _stream(g.device)), "rgbd_point_sample_bwd_emit")
+    skeys, sidx = ordered_sort(keys)
+    ordered_gather(skeys, sidx, coef, gmaps)
+    return dict(keys=keys, coef=coef, sorted_keys=skeys, sorted_idx=sidx, gmaps=gmaps)
+
+
 class _PointSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, maps, coords):
         ctx.save_for_backward(coords)
         ctx.shape = tuple(maps.shape)
+        ctx.deterministic = determinism.is_deterministic()  # the backward runs in the forward's mode
         return _sample(maps, coords)
 
     @staticmethod
@@ -126,6 +149,8 @@ class _PointSample(torch.autograd.Function):
         (coords,) = ctx.saved_tensors
         N, h, w = ctx.shape
         g = gout.float().contiguous()
+        if ctx.deterministic and N and coords.shape[1]:
+            return point_sample_backward_stages(g, coords, h, w)["gmaps"], None
         gmaps = torch.zeros((N, h, w), dtype=torch.float32, device=g.device)
         if N:
             c = coords.float().contiguous()
@@ -310,7 +335,13 @@ class HipMask2FormerLoss(Mask2FormerLoss):
                                     device=dev)
         b_idx, q_idx = self._get_predictions_permutation_indices(indices)
         target_classes.view(-1).index_copy_(0, b_idx * num_queries + q_idx, target_classes_o)
-        loss_ce = criterion(pred_logits.transpose(1, 2), target_classes)
+        if determinism.is_deterministic():
+            # the [B, C, Q] layout takes ATen's 2-d NLL kernel, whose forward adds per-block sums
+            # with float atomics; the same weighted mean over [B Q, C] rows takes the 1-d kernel
+            # (one block, fixed order)
+            loss_ce = criterion(pred_logits.reshape(batch_size * num_queries, -1), target_classes.view(-1))
+        else:
+            loss_ce = criterion(pred_logits.transpose(1, 2), target_classes)
         return {"loss_cross_entropy": loss_ce}
 
     def loss_masks(self, masks_queries_logits, mask_labels, indices, num_masks):

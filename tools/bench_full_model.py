@@ -4,6 +4,8 @@ matcher and 9 auxiliary outputs), backward, AdamW.  Synthetic NYUv2-shaped scene
 instances), random-init weights.  Two arms on the same weights and inputs:
   hip   — hot path (bf16 MFMA) + f1 mask predictor + f2 deformable attention + f3 matcher on HIP
   hf    — hot path (bf16 MFMA), the f1/f2/f3 modules as the installed Hugging Face code
+  hip_det — the hip arm in deterministic mode (rgbd_amd.determinism: atomic-free MSDA and
+          point-sample backward, 1-d class loss); "--arms hip,hip_det" times both modes in one process
 with the HF parts in float32 or under torch.autocast(bfloat16) (--amp).  Prints one JSON line."""
 import argparse
 import json
@@ -27,8 +29,8 @@ def main():
     ap.add_argument("--amp", type=int, default=1)
     ap.add_argument("--arms", default="hip,hf")
     args = ap.parse_args()
-    from rgbd_amd import (deform_attn, dense, init as winit, mask_predictor, masked_attention, point_loss, ops, swin,
-                          synthetic)
+    from rgbd_amd import (deform_attn, dense, determinism, init as winit, mask_predictor, masked_attention, point_loss,
+                          ops, swin, synthetic)
     from rgbd_amd.config import standard_config
     from rgbd_amd.custom_model import CustomMask2FormerForUniversalSegmentation
     dev = torch.device("cuda")
@@ -58,6 +60,9 @@ def main():
                     mod.__class__ = torch.nn.GroupNorm
                 elif type(mod) is dense._FusedReLU:
                     mod.__class__ = torch.nn.ReLU
+        mode_before = determinism.get_state()
+        if arm == "hip_det":
+            determinism.set_deterministic(True)
         opt = torch.optim.AdamW([p for p in m.parameters() if p.requires_grad], lr=1e-5, fused=True)
 
         def step():
@@ -77,11 +82,15 @@ def main():
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
         key = arm if arm not in res else f"{arm}_{ai}"
-        res[key] = {"img_s": round(B / dt, 2), "ms_per_step": round(dt * 1e3, 1), "loss": round(float(loss.detach()), 4)}
+        res[key] = {"img_s": round(B / dt, 2), "ms_per_step": round(dt * 1e3, 1), "loss": round(float(loss.detach()), 4),
+                    "deterministic": determinism.is_deterministic()}
         del m, opt
+        determinism.set_deterministic(mode_before)
         torch.cuda.empty_cache()
     if "hip" in res and "hf" in res:
         res["speedup_hip_vs_hf_modules"] = round(res["hip"]["img_s"] / res["hf"]["img_s"], 3)
+    if "hip" in res and "hip_det" in res:
+        res["slowdown_deterministic"] = round(res["hip_det"]["ms_per_step"] / res["hip"]["ms_per_step"], 3)
     print(json.dumps(res))
 
 
