@@ -365,7 +365,18 @@ int rgbd_adamw_multi_shadow(int n, float* const* params, const float* const* gra
  *     in place (torch semantics, `momentum`), and applies dropout with a counter hash of
  *     `seed` + *seed_counter; the forward then increments *seed_counter on the device (a
  *     u64 the caller owns; NULL = `seed` alone), so a captured graph's replays draw fresh
- *     masks.  training=0 uses the running stats.  B <= 32. */
+ *     masks.  training=0 uses the running stats.  B <= 32.
+ * The dropout stream (training=1) is a contract, replayed by tests/checkers/ratio_dropout.py:
+ *   s = seed + counter (mod 2^64), counter = *seed_counter as the forward finds it (0 if NULL);
+ *   u(seed, i) = the top 24 bits of the splitmix64 finaliser of seed + i * 0x9E3779B97F4A7C15
+ *     (z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *     z ^= z >> 31; all mod 2^64), times 2^-24: a float32 in [0, 1);
+ *   fc_layers.2 (p = 0.3) drops unit o (of 128) of image b when u(s, b * 128 + o) < 0.3f; the
+ *     kept units are divided by 0.7f;
+ *   fc_layers.5 (p = 0.2) drops unit o (of 64) of image b when u(s ^ 0x5555, b * 64 + o) < 0.2f;
+ *     the kept units are divided by 0.8f;
+ *   a dropped unit is +0.0f; the comparisons and divisions are float32;
+ *   a training forward stores counter + 1 into *seed_counter; an eval forward leaves it. */
 #define RGBD_RATIO_NW 24
 #define RGBD_RATIO_NBN 6
 size_t rgbd_ratio_packed_size(int dtype);
@@ -380,6 +391,13 @@ size_t rgbd_ratio_features_offset(int dtype, int B, int H, int W);
  * (conv5 -> BN -> ReLU -> pool, custom_model.py:1412-1416) as rgbd_ratio_forward leaves it:
  * float32 [B][256][4][4] (diagnostics / tests). */
 size_t rgbd_ratio_pooled_offset(int dtype, int B, int H, int W);
+/* Byte offset in the workspace of feature_extractor[4:8] followed by the global average pool
+ * (conv 256->512 -> BN -> ReLU -> mean over the 4x4 map, custom_model.py:1417-1420, :1476-1479)
+ * as rgbd_ratio_forward leaves it: float32 [B][512] (diagnostics / tests). */
+size_t rgbd_ratio_feat_offset(int dtype, int B, int H, int W);
+/* Byte offset in the workspace of fc_layers[0:3] (Linear 512->128 -> ReLU -> Dropout(0.3) when
+ * training) as rgbd_ratio_forward leaves it: float32 [B][128] (diagnostics / tests). */
+size_t rgbd_ratio_hidden_offset(int dtype, int B, int H, int W);
 int rgbd_ratio_forward(int dtype, int training, float momentum, const float* depth3, long long batch_stride,
                        int B, int H, int W, const void* packed, float* const* bn_host, unsigned long long seed,
                        unsigned long long* seed_counter, float* ratio, void* ws, void* stream);

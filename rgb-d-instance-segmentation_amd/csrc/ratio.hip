@@ -2936,6 +2936,14 @@ size_t rgbd_ratio_pooled_offset(int dtype, int B, int H, int W) {
   return make_ws(dtype == RGBD_BF16 ? 2 : 4, B > 0 ? B : 1, H > 0 ? H : 1, W > 0 ? W : 1).pooled;
 }
 
+size_t rgbd_ratio_feat_offset(int dtype, int B, int H, int W) {
+  return make_ws(dtype == RGBD_BF16 ? 2 : 4, B > 0 ? B : 1, H > 0 ? H : 1, W > 0 ? W : 1).feat;
+}
+
+size_t rgbd_ratio_hidden_offset(int dtype, int B, int H, int W) {
+  return make_ws(dtype == RGBD_BF16 ? 2 : 4, B > 0 ? B : 1, H > 0 ? H : 1, W > 0 ? W : 1).h1;
+}
+
 size_t rgbd_ratio_workspace_size(int dtype, int B, int H, int W) {
   return make_ws(dtype == RGBD_BF16 ? 2 : 4, B > 0 ? B : 1, H > 0 ? H : 1, W > 0 ? W : 1).total;
 }

@@ -11,7 +11,13 @@ ragged 90x125), eval with BN + ReLU + pool fused into conv5's epilogue (240x320,
 1280x720) and eval through y (ragged 90x125, 64x96).  Tolerance: rtol 2e-4 / atol 1e-5 of the
 largest pooled value — float32 vs float64 accumulation moves a y value across a bf16 rounding
 boundary for ~1e-4 of the elements, one ulp each, averaged over a pool bin; an indexing slip
-(a wrong tap, channel quarter, bin or tile) is off by orders of magnitude."""
+(a wrong tap, channel quarter, bin or tile) is off by orders of magnitude.
+
+The float32 leg (`test_f32_conv5_bn_relu_pool`): the same stage as the float32 kernels leave it,
+against float64 arithmetic on the float32 gated features (NHWC [B][H][W][128] at
+`rgbd_ratio_features_offset(0, ...)`) and the float32 weights, train (batch statistics, biased
+variance) and eval (running statistics); |got - ref| <= 2e-6 * (1 + max|ref|), a float32 kernel
+against float64 (tests/test_gpu_masked_attention.py's form)."""
 import numpy as np
 import pytest
 import torch
@@ -26,11 +32,11 @@ DEV = "cuda"
 PRE = "model.pixel_level_module.ratio_predictor."
 
 
-def _module():
+def _module(dtype=torch.bfloat16):
     from rgbd_amd.modules import EnhancedDepthImageRatioPredictor
     m = EnhancedDepthImageRatioPredictor(3)
     winit.init_deterministic(m, prefix=PRE)
-    m.compute_dtype = torch.bfloat16
+    m.compute_dtype = dtype
     return m
 
 
@@ -81,3 +87,46 @@ def test_bf16_conv5_bn_relu_pool(B, H, W, training):
     bad = d > 2e-4 * ref.abs() + 1e-5 * scale
     print(f"{B}x{H}x{W} train={training}: max |d| {float(d.max()):.3g} (scale {scale:.3g}), {int(bad.sum())} bad")
     assert not bool(bad.any()), (float(d.max()), scale, np.argwhere(bad.numpy())[:5].tolist())
+
+
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("B,H,W", [(2, 64, 96), (2, 90, 125)])
+def test_f32_conv5_bn_relu_pool(B, H, W, training):
+    from rgbd_amd import _lib, ops
+    pv = gi.pixel_values(21, B, H, W)
+    m = _module(torch.float32)
+    fe = m.feature_extractor
+    bn = fe[1]
+    g = torch.Generator().manual_seed(5)
+    bn.running_mean.copy_(torch.randn(256, generator=g) * 0.05)
+    bn.running_var.copy_(torch.rand(256, generator=g) * 0.5 + 0.5)
+    run_mean, run_var = bn.running_mean.clone().double(), bn.running_var.clone().double()
+    m = m.to(DEV).train(training)
+    x = torch.from_numpy(pv).to(DEV)[:, 3:6]
+    with torch.no_grad():
+        m(x)
+    torch.cuda.synchronize()
+    L = _lib.lib()
+    ws = ops._workspace(x.device, L.rgbd_ratio_workspace_size(0, B, H, W), "ratio")
+    off = L.rgbd_ratio_features_offset(0, B, H, W)
+    xin = ws[off:off + B * H * W * 128 * 4].view(torch.float32).reshape(B, H, W, 128).permute(0, 3, 1, 2).double().cpu()
+    poff = L.rgbd_ratio_pooled_offset(0, B, H, W)
+    got = ws[poff:poff + B * 256 * 16 * 4].view(torch.float32).reshape(B, 256, 4, 4).double().cpu()
+    assert float(xin.abs().max()) > 1e-3
+
+    conv = fe[0]
+    y = F.conv2d(xin, conv.weight.detach().cpu().double(), conv.bias.detach().cpu().double(), padding=1)
+
+    def pooled(mean, var):
+        sc = bn.weight.detach().cpu().double() / torch.sqrt(var + 1e-5)
+        z = (y - mean[None, :, None, None]) * sc[None, :, None, None] + bn.bias.detach().cpu().double()[None, :, None, None]
+        return F.adaptive_avg_pool2d(torch.relu(z), 4)
+    batch = (y.mean((0, 2, 3)), y.var((0, 2, 3), unbiased=False))
+    ref = pooled(*(batch if training else (run_mean, run_var)))
+    other = pooled(*((run_mean, run_var) if training else batch))
+    tol = 2e-6 * (1 + float(ref.abs().max()))
+    err = float((got - ref).abs().max())
+    print(f"f32 {B}x{H}x{W} train={training}: max |d| {err:.3g} (tol {tol:.3g}, max|ref| {float(ref.abs().max()):.3g}); "
+          f"the other kind of statistics is {float((other - ref).abs().max()):.3g} away")
+    assert float((other - ref).abs().max()) > 100 * tol  # batch and running statistics differ here
+    assert err <= tol
