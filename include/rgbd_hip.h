@@ -716,6 +716,34 @@ int rgbd_groupnorm_bwd(int x_dtype, const void* x, int dy_dtype, const void* dy,
 int rgbd_swin_window_attn(int dtype, const void* q, const void* k, const void* v, long long ldq, const float* bq,
                           const float* bk, const float* bv, const float* table, int B, int H, int W, int heads,
                           int window, int shift, float scale, void* out, long long ldo, void* stream);
+/* rgbd_swin_window_attn_bwd: the gradient of rgbd_swin_window_attn, same arguments plus
+ * dout dtype [B*H*W][ldo].  S and P are recomputed as the forward computes them (nothing of the
+ * forward is kept; D_q = sum_d dO O is taken as sum_k P dP, i.e. with O recomputed), then
+ *   dV = P^T dO, dP = dO V^T, dS = P o (dP - D), dQ = scale dS K, dK = scale dS^T Q,
+ *   dtable[idx(q, k)][h] += dS[q][k].
+ * dq / dk / dv: dtype rows [B*H*W][ldd] (ldd = 3C when they are the three column blocks of one
+ *   [rows][3C] buffer, the dY of the qkv GEMM), every row written exactly once;
+ * dbk / dbv float32 [C] (may be NULL): the dK / dV rows of the padded-map tokens, whose k / v are
+ *   the projection biases — exactly zero when H and W are multiples of 7, and to be ADDED by the
+ *   caller to the column sums of dk / dv.  There is no dbq: a padded token's output row is
+ *   cropped, so its dQ is zero;
+ * dtable float32 [169][heads].  All outputs are OVERWRITTEN.  ws:
+ *   rgbd_swin_window_attn_bwd_workspace_size(B, H, W, heads) bytes (per-(image, window, head)
+ *   partials of dtable / dbk / dbv, summed by a second kernel in a fixed order: no float atomics,
+ *   bitwise reproducible); it needs no zeroing.  B*H*W < 2^31. */
+size_t rgbd_swin_window_attn_bwd_workspace_size(int B, int H, int W, int heads);
+int rgbd_swin_window_attn_bwd(int dtype, const void* q, const void* k, const void* v, long long ldq, const float* bq,
+                              const float* bk, const float* bv, const float* table, const void* dout, long long ldo,
+                              int B, int H, int W, int heads, int window, int shift, float scale, void* dq, void* dk,
+                              void* dv, long long ldd, float* dbk, float* dbv, float* dtable, void* ws,
+                              void* stream);
+/* The exact (erf) GELU of Swin's MLP, elementwise over n contiguous elements (csrc/act.hip), for
+ * the layers' training path (without gradients the GELU stays in fc1's GEMM epilogue):
+ *   rgbd_gelu: m = 0.5 u (1 + erf(u / sqrt 2)), the epilogue's formula (bit-identical in float32);
+ *   rgbd_gelu_bwd: du = dm (0.5 (1 + erf(u / sqrt 2)) + u exp(-u^2 / 2) / sqrt(2 pi)).
+ * dtype RGBD_F32 / RGBD_BF16 (float32 arithmetic); 16-byte aligned pointers. */
+int rgbd_gelu(int dtype, const void* u, void* m, long long n, void* stream);
+int rgbd_gelu_bwd(int dtype, const void* u, const void* dm, void* du, long long n, void* stream);
 
 /* ---------------------------------------------------------------- kernel timing (bench only)
  * When enabled, launch functions bracket their main kernel with hipEvents recorded on the

@@ -134,6 +134,11 @@ SIGNATURES = {
     "rgbd_groupnorm_bwd": (_I, [_I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rgbd_swin_window_attn": (_I, [_I, _P, _P, _P, _LL, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P,
                                    _LL, _P]),
+    "rgbd_swin_window_attn_bwd_workspace_size": (_SZ, [_I, _I, _I, _I]),
+    "rgbd_swin_window_attn_bwd": (_I, [_I, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I,
+                                       ctypes.c_float, _P, _P, _P, _LL, _P, _P, _P, _P, _P]),
+    "rgbd_gelu": (_I, [_I, _P, _P, _LL, _P]),
+    "rgbd_gelu_bwd": (_I, [_I, _P, _P, _P, _LL, _P]),
     "rgbd_timing_enable": (_I, [_I]),
     "rgbd_timing_read": (ctypes.c_double, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     "rgbd_ratio_packed_size": (_SZ, [_I]),

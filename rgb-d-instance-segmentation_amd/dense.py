@@ -10,8 +10,9 @@ Reference call sites (transformers 5.15, the modules the reference model instant
     fc1 -> relu -> fc2, three post-norm LayerNorms;
   * pixel decoder encoder layer ``Mask2FormerPixelDecoderEncoderLayer.forward`` (:1036-1102):
     deformable-attention projections, fc1 -> relu -> fc2, two LayerNorms;
-  * Swin-T (modeling_swin.py): every nn.Linear / nn.LayerNorm of the backbone (forward only in
-    v0.4.0: the reference detaches the colour features, custom_model.py:332-333).
+  * Swin-T (modeling_swin.py): every nn.Linear / nn.LayerNorm of the backbone, forward and
+    backward (v0.4.0 only needs the forward: the reference detaches the colour features,
+    custom_model.py:332-333; the RGB baseline 0.0.0 trains the encoder).
 
 Precision follows the module being replaced: float32 inputs run the exact-f32 MFMA GEMMs; under
 torch.autocast(bfloat16) the GEMMs take bf16 operands (activations and weights cast per call)
@@ -23,7 +24,9 @@ float32 straight from the bf16 GEMM (autocast's path rounds them to bf16 first).
 nn.Conv2d -> conv.HipConv2d (1x1, 3x3 and Swin's 4x4 patch embedding as GEMMs), nn.Linear -> HipLinear, nn.LayerNorm -> HipLayerNorm, the decoder and pixel-decoder encoder
 layers -> classes whose forward fuses the ReLU into fc1's epilogue and its gradient into
 fc2's dX epilogue.  Inputs the kernels do not cover (CPU tensors, float16, LayerNorm width
-> 1536, dropout in training, GELU with gradients) take the module's own torch path.
+> 1536, dropout in training) take the module's own torch path.  GELU (Swin's MLP) is fused into
+fc1's epilogue when no gradient is needed; with gradients fc1 keeps its pre-activation and the
+GELU and its gradient are elementwise kernels (rgbd_gelu / rgbd_gelu_bwd).
 """
 import math
 
@@ -127,6 +130,21 @@ def colsum(y2):
     return out
 
 
+def gelu(u):
+    """erf GELU of u (contiguous), the formula of the GEMM's fused epilogue, as its own kernel."""
+    m = torch.empty_like(u)
+    check(_lib.lib().rgbd_gelu(_CODE[u.dtype], _p(u), _p(m), u.numel(), _stream(u.device)), "rgbd_gelu")
+    return m
+
+
+def gelu_bwd(u, dm):
+    """du = dm * gelu'(u); u and dm contiguous, of one dtype."""
+    du = torch.empty_like(u)
+    check(_lib.lib().rgbd_gelu_bwd(_CODE[u.dtype], _p(u), _p(dm), _p(du), u.numel(), _stream(u.device)),
+          "rgbd_gelu_bwd")
+    return du
+
+
 def _rows(x, dt):
     """x as contiguous [rows, C] in dt.  A cast is made once per tensor (and version): it is
     kept on x, so the projections that share an input (q / k of the self-attention, the sampling
@@ -165,28 +183,34 @@ def _dx(g2, wc, M, K, N, act=ACT_NONE, R=None, out_dtype=None):
 
 
 class LinearFunction(torch.autograd.Function):
-    """y = act(x W^T + b), act none / relu / gelu (gelu: forward only)."""
+    """y = act(x W^T + b), act none / relu / gelu.  GELU is fused into the epilogue when no input
+    needs a gradient; otherwise the pre-activation is kept and the GELU is its own kernel."""
 
     @staticmethod
     def forward(ctx, x, w, b, act, dt):
         N, K = w.shape
         x2 = _rows(x, dt)
         wc = cast_weight(w, dt)
-        y = _fwd(x2, wc, b, act, x2.shape[0], N, K)
-        ctx.save_for_backward(x2, wc, y if act == ACT_RELU else None)
+        if act == ACT_GELU and any(ctx.needs_input_grad[:3]):
+            kept = _fwd(x2, wc, b, ACT_NONE, x2.shape[0], N, K)
+            y = gelu(kept)
+        else:
+            y = _fwd(x2, wc, b, act, x2.shape[0], N, K)
+            kept = y if act == ACT_RELU else None
+        ctx.save_for_backward(x2, wc, kept)
         ctx.act, ctx.x_dtype, ctx.w_dtype, ctx.has_b = act, x.dtype, w.dtype, b is not None
         return y.view(*x.shape[:-1], N)
 
     @staticmethod
     def backward(ctx, gy):
         x2, wc, y = ctx.saved_tensors
-        if ctx.act == ACT_GELU:
-            raise RuntimeError("HipLinear: the fused GELU epilogue is forward-only")
         M, K = x2.shape
         N = wc.shape[0]
         g2 = _rows(gy, x2.dtype)
         if ctx.act == ACT_RELU:
             g2 = g2 * (y > 0)
+        elif ctx.act == ACT_GELU:  # y holds the pre-activation
+            g2 = gelu_bwd(y, g2)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = _dx(g2, wc, M, K, N, out_dtype=ctx.x_dtype).to(ctx.x_dtype).view(*gy.shape[:-1], K)
@@ -226,6 +250,71 @@ class FFNFunction(torch.autograd.Function):
         dw1 = gemm(dh, x2, 1, 1, F_, K, M, c_f32=True).to(ctx.w_dtypes[0])
         db1 = colsum(dh)
         return dx, dw1, db1, dw2, db2, None
+
+
+class LinearResidualFunction(torch.autograd.Function):
+    """y = x W^T + b + R with the residual in the GEMM epilogue (R and y float32 when ``c_f32``:
+    autocast's float32 residual stream around bf16 GEMMs).  The residual's gradient is the
+    incoming gradient itself: no launch."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, R, dt, c_f32):
+        N, K = w.shape
+        x2 = _rows(x, dt)
+        wc = cast_weight(w, dt)
+        y = gemm(x2, wc, 0, 0, x2.shape[0], N, K, bias=b, R=R, c_f32=c_f32)
+        ctx.save_for_backward(x2, wc)
+        ctx.x_dtype, ctx.w_dtype, ctx.has_b = x.dtype, w.dtype, b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x2, wc = ctx.saved_tensors
+        M, K = x2.shape
+        N = wc.shape[0]
+        g2 = _rows(gy, x2.dtype)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _dx(g2, wc, M, K, N, out_dtype=ctx.x_dtype).to(ctx.x_dtype)
+        if ctx.needs_input_grad[1]:
+            dw = gemm(g2, x2, 1, 1, N, K, M, c_f32=True).to(ctx.w_dtype)
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            db = colsum(g2)
+        return dx, dw, db, gy if ctx.needs_input_grad[3] else None, None, None
+
+
+class GeluFFNFunction(torch.autograd.Function):
+    """fc2(gelu(fc1(x))) + R, the GELU variant of FFNFunction for Swin's MLP with gradients: fc1
+    stores its pre-activation u, m = gelu(u) and du = dm gelu'(u) are elementwise kernels (one
+    extra pass each way next to the fused epilogue), the residual stays in fc2's epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, R, dt, c_f32):
+        F_, K = w1.shape
+        N = w2.shape[0]
+        x2 = _rows(x, dt)
+        w1c, w2c = cast_weight(w1, dt), cast_weight(w2, dt)
+        M = x2.shape[0]
+        u = gemm(x2, w1c, 0, 0, M, F_, K, bias=b1)
+        m = gelu(u)
+        y = gemm(m, w2c, 0, 0, M, N, F_, bias=b2, R=R, c_f32=c_f32)
+        ctx.save_for_backward(x2, u, m, w1c, w2c)
+        ctx.x_dtype, ctx.w_dtypes = x.dtype, (w1.dtype, w2.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x2, u, m, w1c, w2c = ctx.saved_tensors
+        M, K = x2.shape
+        F_, N = u.shape[1], w2c.shape[0]
+        g2 = _rows(gy, x2.dtype)
+        du = gelu_bwd(u, _dx(g2, w2c, M, F_, N))
+        dw2 = gemm(g2, m, 1, 1, N, F_, M, c_f32=True).to(ctx.w_dtypes[1])
+        db2 = colsum(g2)
+        dx = _dx(du, w1c, M, K, F_, out_dtype=ctx.x_dtype).to(ctx.x_dtype)
+        dw1 = gemm(du, x2, 1, 1, F_, K, M, c_f32=True).to(ctx.w_dtypes[0])
+        db1 = colsum(du)
+        return dx, dw1, db1, dw2, db2, gy if ctx.needs_input_grad[5] else None, None, None
 
 
 class LayerNormFunction(torch.autograd.Function):
