@@ -158,19 +158,14 @@ int rgbd_dggm_fuse_bwd(int dtype, const void* dout, const float* grad, const flo
 
 /* All backbone scales in one launch (the fused hot path calls these): n <= 4 scales given as
  * host arrays of device pointers and sizes; same arithmetic per element as the single-scale
- * forms (bitwise identical results).  cp1_host may be NULL (no residual); workspace for the
- * backward from rgbd_dggm_fuse_bwd_multi_workspace_size. */
-int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, const void* const* color_host,
-                             void* const* out_host, const float* const* weight_host, const float* const* bias_host,
-                             const int* C_host, const int* h_host, const int* w_host, const float* grad,
-                             const float* mask, long long pv_batch_stride, int B, int H, int W, void* stream);
-/* rgbd_dggm_fuse_fwd_multi with per-scale cp1 layout: bit k of cp1_nhwc_mask set = scale k's cp1
- * is NHWC dtype [B][h][w][C] (C % 8 == 0; the DSAM cascade's layout), else NCHW. */
-int rgbd_dggm_fuse_fwd_multi_mixed(int dtype, int n, const void* const* cp1_host, int cp1_nhwc_mask,
-                                   const void* const* color_host, void* const* out_host,
-                                   const float* const* weight_host, const float* const* bias_host, const int* C_host,
-                                   const int* h_host, const int* w_host, const float* grad, const float* mask,
-                                   long long pv_batch_stride, int B, int H, int W, void* stream);
+ * forms (bitwise identical results).  cp1_host may be NULL (no residual); bit k of cp1_nhwc_mask
+ * set = scale k's cp1 is NHWC dtype [B][h][w][C] (C % 8 == 0; the DSAM cascade's layout), else
+ * NCHW.  Workspace for the backward from rgbd_dggm_fuse_bwd_multi_workspace_size. */
+int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, int cp1_nhwc_mask,
+                             const void* const* color_host, void* const* out_host, const float* const* weight_host,
+                             const float* const* bias_host, const int* C_host, const int* h_host, const int* w_host,
+                             const float* grad, const float* mask, long long pv_batch_stride, int B, int H, int W,
+                             void* stream);
 size_t rgbd_dggm_fuse_bwd_multi_workspace_size(int n, const int* C_host, const int* h_host, const int* w_host,
                                                int B);
 int rgbd_dggm_fuse_bwd_multi(int dtype, int n, const void* const* dout_host, const float* const* weight_host,
@@ -226,66 +221,20 @@ int rgbd_dsam_code_masks(int n, const uint8_t* const* codes_host, const long lon
                          uint32_t* masks, void* stream);
 
 /* ---------------------------------------------------------------- K5 DSAM masked conv
- * Forward of one DSAModule for the whole batch (replaces the per-sample Python loop of
- * custom_model.py:339-352 and DSAModule.forward :682-699):
- *   out = residual + sum_{i<4} Conv3x3s2_i(x * m_i) + sum_{i<n_masks[b]} b_i + Proj3x3s2(x)
- * x_nhwc: dtype [B][h][w][Cin]; code: uint8 [B][h][w] (pooled region codes at x's
- * resolution); bias float32 [4][Cout]; residual/out_nchw: dtype [B][Cout][ho][wo];
- * out_nhwc (optional, may be NULL): dtype [B][ho][wo][Cout].  ws: workspace of
- * rgbd_dsam_conv_workspace_size bytes (split-K slabs of the bf16 path). */
-size_t rgbd_dsam_conv_workspace_size(int dtype, int B, int Cin, int h, int w, int Cout);
-int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                  int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                  const void* residual, void* out_nchw, void* out_nhwc, void* ws, void* stream);
-/* The same forward with everything in NHWC (RGBD_BF16 only; the hot path's cascade): residual_nhwc
- * (may be NULL) and out_nhwc dtype [B][ho][wo][Cout]; no NCHW output.  Same arithmetic and
- * rounding as rgbd_dsam_fwd (res + (acc + bias), one rounding). */
-int rgbd_dsam_fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                       int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                       const void* residual_nhwc, void* out_nhwc, void* ws, void* stream);
-/* rgbd_dsam_fwd_nhwc with a float32 interface (compute dtype RGBD_BF16, anything else:
- * RGBD_E_DTYPE; the operands x_nhwc / wfwd stay bf16): with v = acc + bias, the float32 value the
- * epilogue holds before the residual,
- *   out_f32_nhwc (float32 [B][ho][wo][Cout], optional) = residual_f32_nhwc + v   (one float32 add)
- *   out_nhwc     (bf16    [B][ho][wo][Cout], optional) = RNE(out_f32_nhwc)       (one rounding)
- * residual_f32_nhwc: float32 [B][ho][wo][Cout], optional (NULL: v itself).  At least one output;
- * both float32 pointers 16-byte aligned.  A bf16 residual_nhwc is accepted only with both float32
- * pointers NULL, and the call is then rgbd_dsam_fwd_nhwc (RGBD_E_ARG otherwise).  With a residual
- * whose values are bf16-representable, out_nhwc is bitwise rgbd_dsam_fwd_nhwc's.  Workspace,
- * plans (RGBD_LEG_FWD) and argument checks are those of rgbd_dsam_fwd_nhwc[_planned]. */
-int rgbd_dsam_fwd_nhwc_f32io(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                             int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                             const void* residual_nhwc, void* out_nhwc, void* ws, void* stream,
-                             const float* residual_f32_nhwc, float* out_f32_nhwc);
-/* dX of one DSAModule, plus the upstream gradient of its input's other consumer:
- *   dx = gin + sum_i m_i * ConvT_i(gout) + ConvT_proj(gout)
- * gout_nhwc: dtype [B][ho][wo][Cout].  At least one of dx_nchw (dtype [B][Cin][h][w]) and
- * dx_nhwc (dtype [B][h][w][Cin]) is written.  The optional gin comes in the layout of the pass
- * that adds it: gin_nchw (dtype [B][Cin][h][w]) when dx_nchw is written, gin_nhwc (RGBD_BF16
- * only, [B][h][w][Cin]) when only dx_nhwc is (the hot path's cascade: NHWC in, NHWC out). */
-int rgbd_dsam_bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h,
-                       int w, int Cout, const void* wbwd, const void* gin_nchw, const void* gin_nhwc,
-                       void* dx_nchw, void* dx_nhwc, void* ws, void* stream);
-/* dW / db of one DSAModule: dconv_w float32 [4][Cout][Cin][3][3], dproj_w float32
- * [Cout][Cin][3][3], dbias float32 [4][Cout] (all OVERWRITTEN).  gout_nchw: dtype
- * [B][Cout][ho][wo] (required for RGBD_F32; optional for RGBD_BF16, whose bias sums then read
- * gout_nhwc); gout_nhwc: the same gradient as [B][ho][wo][Cout] (required for RGBD_BF16,
- * ignored for RGBD_F32); x_nhwc as in the forward. */
-size_t rgbd_dsam_bwd_weight_workspace_size(int dtype, int B, int Cin, int h, int w, int Cout);
-int rgbd_dsam_bwd_weight(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
-                         const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h,
-                         int w, int Cout, float* dconv_w, float* dproj_w, float* dbias, void* ws,
-                         void* stream);
-
-/* Planning ahead (RGBD_BF16).  What a bf16 leg sets up before its GEMM (per-tile code sets and
- * the work list of a forward / dX leg; per-code live units, items and tap masks of a dW leg)
- * depends only on the region codes, so a caller may plan every leg of a step at once, right
- * after rgbd_edsam_decompose (two launches for all forward / dX legs), and run the legs later
- * with the _planned entry points: same arguments as the plain ones plus the leg's plan buffer,
- * and ws then needs only rgbd_dsam_run_workspace_size bytes (split-K / dW partials, which legs
- * run one after another on one stream may share).  Results are bitwise those of the plain
- * entry points.  A plan buffer serves one run of one leg (the run uses up its work counters):
- * plan again before running the leg again, and leave the buffer untouched until the leg ran. */
+ * Plan and workspace of a leg (forward, dX or dW of one DSAModule).
+ * RGBD_BF16 legs run from a plan.  What a leg sets up before its GEMM (per-tile code sets and the
+ * work list of a forward / dX leg; per-code live units, items and tap masks of a dW leg) depends
+ * only on the region codes, so rgbd_dsam_plan writes it into a buffer of rgbd_dsam_plan_size
+ * bytes per leg: any number of legs per call (two launches for all forward / dX legs, three for
+ * all dW legs), e.g. every leg of a step right after rgbd_edsam_decompose.  The run calls below
+ * take the leg's plan (NULL: RGBD_E_ARG) and a workspace ws of rgbd_dsam_run_workspace_size
+ * bytes: the partial tiles of a forward / dX leg, [partials | channel sums] of a dW leg; legs
+ * run one after another on one stream may share it.  A plan serves one run of one leg (the run
+ * uses up its work counters): plan again before running the leg again, and leave the buffer
+ * untouched until the leg ran.
+ * RGBD_F32 legs have no plan (plan = NULL; a plan given is refused, with the status noted at
+ * each call); ws is rgbd_dsam_run_workspace_size(RGBD_F32, ...) bytes as well: 256 for forward
+ * and dX (unused), [split partials | channel sums] for dW. */
 enum { RGBD_LEG_FWD = 0, RGBD_LEG_DX = 1, RGBD_LEG_DW = 2 };
 typedef struct rgbd_dsam_leg {
   int kind;                /* RGBD_LEG_* */
@@ -294,32 +243,61 @@ typedef struct rgbd_dsam_leg {
   void* plan;              /* rgbd_dsam_plan_size bytes (device), OVERWRITTEN */
 } rgbd_dsam_leg;
 size_t rgbd_dsam_plan_size(int kind, int B, int Cin, int h, int w, int Cout);
-size_t rgbd_dsam_run_workspace_size(int kind, int B, int Cin, int h, int w, int Cout);
 int rgbd_dsam_plan(int n, const rgbd_dsam_leg* legs, void* stream);  /* legs: host array */
-int rgbd_dsam_fwd_nhwc_planned(int dtype, const void* x_nhwc, const uint8_t* code,
-                               const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
-                               const void* wfwd, const float* bias, const void* residual_nhwc,
-                               void* out_nhwc, const void* plan, void* ws, void* stream);
-int rgbd_dsam_fwd_nhwc_f32io_planned(int dtype, const void* x_nhwc, const uint8_t* code,
-                                     const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
-                                     const void* wfwd, const float* bias, const void* residual_nhwc, void* out_nhwc,
-                                     const void* plan, void* ws, void* stream, const float* residual_f32_nhwc,
-                                     float* out_f32_nhwc);
-int rgbd_dsam_bwd_data_planned(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin,
-                               int h, int w, int Cout, const void* wbwd, const void* gin_nchw,
-                               const void* gin_nhwc, void* dx_nchw, void* dx_nhwc, const void* plan,
-                               void* ws, void* stream);
-int rgbd_dsam_bwd_weight_planned(int dtype, const void* gout_nchw, const void* gout_nhwc,
-                                 const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                                 int B, int Cin, int h, int w, int Cout, float* dconv_w, float* dproj_w,
-                                 float* dbias, const void* plan, void* ws, void* stream);
+size_t rgbd_dsam_run_workspace_size(int dtype, int kind, int B, int Cin, int h, int w, int Cout);
+
+/* Forward of one DSAModule for the whole batch (replaces the per-sample Python loop of
+ * custom_model.py:339-352 and DSAModule.forward :682-699):
+ *   out = residual + sum_{i<4} Conv3x3s2_i(x * m_i) + sum_{i<n_masks[b]} b_i + Proj3x3s2(x)
+ * x_nhwc: dtype [B][h][w][Cin]; code: uint8 [B][h][w] (pooled region codes at x's
+ * resolution); bias float32 [4][Cout]; residual/out_nchw: dtype [B][Cout][ho][wo];
+ * out_nhwc (optional, may be NULL): dtype [B][ho][wo][Cout].  A plan with RGBD_F32: RGBD_E_DTYPE. */
+int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
+                  int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
+                  const void* residual, void* out_nchw, void* out_nhwc, const void* plan, void* ws,
+                  void* stream);
+/* The same forward with everything in NHWC (RGBD_BF16 only, anything else: RGBD_E_DTYPE; the hot
+ * path's cascade), no NCHW output; the operands x_nhwc / wfwd are bf16.  With v = acc + bias, the
+ * float32 value the epilogue holds before the residual, either the bf16 interface
+ *   out_nhwc (bf16 [B][ho][wo][Cout]) = RNE(residual_nhwc + v)   (residual_nhwc bf16, optional)
+ * with both float32 pointers NULL (rgbd_dsam_fwd's arithmetic and rounding), or the float32 one
+ *   out_f32_nhwc (float32 [B][ho][wo][Cout], optional) = residual_f32_nhwc + v   (one float32 add)
+ *   out_nhwc     (bf16    [B][ho][wo][Cout], optional) = RNE(out_f32_nhwc)       (one rounding)
+ * residual_f32_nhwc: float32 [B][ho][wo][Cout], optional (NULL: v itself).  At least one output;
+ * both float32 pointers 16-byte aligned; a bf16 residual_nhwc beside a float32 pointer is
+ * RGBD_E_ARG.  With a residual whose values are bf16-representable, the float32 interface's
+ * out_nhwc is bitwise the bf16 interface's. */
+int rgbd_dsam_fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
+                       int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
+                       const void* residual_nhwc, void* out_nhwc, const float* residual_f32_nhwc,
+                       float* out_f32_nhwc, const void* plan, void* ws, void* stream);
+/* dX of one DSAModule, plus the upstream gradient of its input's other consumer:
+ *   dx = gin + sum_i m_i * ConvT_i(gout) + ConvT_proj(gout)
+ * gout_nhwc: dtype [B][ho][wo][Cout].  At least one of dx_nchw (dtype [B][Cin][h][w]) and
+ * dx_nhwc (dtype [B][h][w][Cin]) is written.  The optional gin comes in the layout of the pass
+ * that adds it: gin_nchw (dtype [B][Cin][h][w]) when dx_nchw is written, gin_nhwc (RGBD_BF16
+ * only, [B][h][w][Cin]) when only dx_nhwc is (the hot path's cascade: NHWC in, NHWC out).
+ * A plan with RGBD_F32: RGBD_E_DTYPE. */
+int rgbd_dsam_bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h,
+                       int w, int Cout, const void* wbwd, const void* gin_nchw, const void* gin_nhwc,
+                       void* dx_nchw, void* dx_nhwc, const void* plan, void* ws, void* stream);
+/* dW / db of one DSAModule: dconv_w float32 [4][Cout][Cin][3][3], dproj_w float32
+ * [Cout][Cin][3][3], dbias float32 [4][Cout] (all OVERWRITTEN).  gout_nchw: dtype
+ * [B][Cout][ho][wo] (required for RGBD_F32; optional for RGBD_BF16, whose bias sums then read
+ * gout_nhwc); gout_nhwc: the same gradient as [B][ho][wo][Cout] (required for RGBD_BF16,
+ * ignored for RGBD_F32); x_nhwc as in the forward.  A plan with RGBD_F32: RGBD_E_ARG. */
+int rgbd_dsam_bwd_weight(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
+                         const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h,
+                         int w, int Cout, float* dconv_w, float* dproj_w, float* dbias, const void* plan,
+                         void* ws, void* stream);
 /* dW of several bf16 DSAM legs that are ready together (the hot path's dsam1 and dsam0 once the dX
  * cascade has finished; hot_path.py): one persistent GEMM launch over the legs' joint work list —
  * two back-to-back whole-chip launches would each drain on a partly idle chip; its workgroups
- * then drain the legs' bias channel sums — and one launch for both legs' combines.  Per leg the results are bitwise those of rgbd_dsam_bwd_weight_planned
- * with gout_nchw = NULL (the autograd of DSAModule.forward, custom_model.py:682-699).  n: 1 or 2;
- * every run has its own plan and ws (rgbd_dsam_run_workspace_size(RGBD_LEG_DW, ...)).  Legs of
- * different output tile shapes run one launch each. */
+ * then drain the legs' bias channel sums — and one launch for both legs' combines.  Per leg the
+ * results are bitwise those of rgbd_dsam_bwd_weight with gout_nchw = NULL (the autograd of
+ * DSAModule.forward, custom_model.py:682-699).  n: 1 or 2; every run has its own plan and ws
+ * (rgbd_dsam_run_workspace_size(RGBD_BF16, RGBD_LEG_DW, ...)).  Legs of different output tile
+ * shapes run one launch each. */
 typedef struct rgbd_dsam_dw_run {
   const void* gout_nhwc;   /* upstream gradient [B][ho][wo][Cout] bf16 (device) */
   const void* x_nhwc;      /* the DSAM's input [B][h][w][Cin] bf16 (device) */
@@ -331,8 +309,8 @@ typedef struct rgbd_dsam_dw_run {
   const void* plan;        /* this leg's RGBD_LEG_DW plan (rgbd_dsam_plan) */
   void* ws;
 } rgbd_dsam_dw_run;
-int rgbd_dsam_bwd_weight_planned_multi(int n, const rgbd_dsam_dw_run* runs, const rgbd_decomp_info* info,
-                                       void* stream);  /* runs: host array */
+int rgbd_dsam_bwd_weight_multi(int n, const rgbd_dsam_dw_run* runs, const rgbd_decomp_info* info,
+                               void* stream);  /* runs: host array */
 
 /* ---------------------------------------------------------------- optimizer step
  * AdamW (the HF Trainer's optimizer, finetuning.py:98, lr 1e-5 constant per config.json:12-13) over
@@ -398,16 +376,14 @@ size_t rgbd_ratio_feat_offset(int dtype, int B, int H, int W);
 /* Byte offset in the workspace of fc_layers[0:3] (Linear 512->128 -> ReLU -> Dropout(0.3) when
  * training) as rgbd_ratio_forward leaves it: float32 [B][128] (diagnostics / tests). */
 size_t rgbd_ratio_hidden_offset(int dtype, int B, int H, int W);
+/* flags: option bits (0: none; another bit: RGBD_E_ARG).  RGBD_RATIO_F_PHASE2 runs the bf16 train
+ * mode's gated features through the phase-2 recompute (stem + fusion) instead of the gate kernel
+ * over phase 1's stored fusion output — the same values by another route, for tests that compare
+ * the two. */
+#define RGBD_RATIO_F_PHASE2 1
 int rgbd_ratio_forward(int dtype, int training, float momentum, const float* depth3, long long batch_stride,
                        int B, int H, int W, const void* packed, float* const* bn_host, unsigned long long seed,
-                       unsigned long long* seed_counter, float* ratio, void* ws, void* stream);
-/* The same with option bits: RGBD_RATIO_F_PHASE2 runs the bf16 train mode's gated features
- * through the phase-2 recompute (stem + fusion) instead of the gate kernel over phase 1's stored
- * fusion output — the same values by another route, for tests that compare the two. */
-#define RGBD_RATIO_F_PHASE2 1
-int rgbd_ratio_forward_ex(int dtype, int training, float momentum, const float* depth3, long long batch_stride,
-                          int B, int H, int W, const void* packed, float* const* bn_host, unsigned long long seed,
-                          unsigned long long* seed_counter, float* ratio, void* ws, int flags, void* stream);
+                       unsigned long long* seed_counter, float* ratio, void* ws, int flags, void* stream);
 
 /* ---------------------------------------------------------------- f3 point-sampled mask terms
  * The mask terms of the Mask2Former matcher and loss (transformers 5.15 modeling_mask2former.py,
@@ -424,12 +400,10 @@ int rgbd_ratio_forward_ex(int dtype, int training, float momentum, const float* 
  * rgbd_point_losses: per row n of logits / labels [N][P]: ce[n] = mean BCEWithLogits, dice[n] =
  *   1 - (2 sum sig*y + 1) / (sum sig + sum y + 1), sums[n] = (sum sig*y, sum sig, sum y);
  *   rgbd_point_losses_bwd: glogits [N][P] from the per-row upstream gradients g_ce, g_dice [N]. */
-int rgbd_point_sample(const float* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord, int P,
-                      float* out, void* stream);
-/* the same sample from maps of dtype RGBD_F32 or RGBD_BF16 (widened exactly: the bf16 logits
- * the model produces under autocast are sampled without a float32 copy); f32 output */
-int rgbd_point_sample_t(int dtype, const void* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord,
-                        int P, float* out, void* stream);
+/* maps of dtype RGBD_F32 or RGBD_BF16 (widened exactly: the bf16 logits the model produces under
+ * autocast are sampled without a float32 copy); f32 output */
+int rgbd_point_sample(int dtype, const void* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord,
+                      int P, float* out, void* stream);
 /* the same with the point set of map m given per map: coords [S][P][2], set_of_map int [nmaps]
  * (device) — every image's target masks against that image's points in one launch (the matcher
  * draws one point set per image, modeling_mask2former.py:459-463) */

@@ -54,9 +54,7 @@ SIGNATURES = {
     "rgbd_dggm_fuse_fwd": (_I, [_I, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rgbd_dggm_fuse_bwd_workspace_size": (_SZ, [_I, _I, _I, _I]),
     "rgbd_dggm_fuse_bwd": (_I, [_I, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dggm_fuse_fwd_multi": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
-    "rgbd_dggm_fuse_fwd_multi_mixed": (_I, [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I,
-                                            _P]),
+    "rgbd_dggm_fuse_fwd_multi": (_I, [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
     "rgbd_dggm_fuse_bwd_multi_workspace_size": (_SZ, [_I, _P, _P, _P, _I]),
     "rgbd_dggm_fuse_bwd_multi": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P, _P]),
     "rgbd_nchw_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
@@ -69,24 +67,15 @@ SIGNATURES = {
     "rgbd_dsam_packed_elems": (_LL, [_I, _I, _I]),
     "rgbd_dsam_pack_weights": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "rgbd_dsam_code_masks": (_I, [_I, _P, _P, _P, _P]),
-    "rgbd_dsam_conv_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "rgbd_dsam_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_fwd_nhwc": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_bwd_data": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_bwd_weight_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "rgbd_dsam_bwd_weight": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rgbd_dsam_plan_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "rgbd_dsam_run_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "rgbd_dsam_plan": (_I, [_I, _P, _P]),
-    "rgbd_dsam_fwd_nhwc_planned": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_fwd_nhwc_f32io": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_fwd_nhwc_f32io_planned": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                                              _P]),
-    "rgbd_dsam_bwd_data_planned": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_bwd_weight_planned": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "rgbd_dsam_bwd_weight_planned_multi": (_I, [_I, _P, _P, _P]),
-    "rgbd_point_sample": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
-    "rgbd_point_sample_t": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    "rgbd_dsam_run_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
+    "rgbd_dsam_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_fwd_nhwc": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_bwd_data": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_bwd_weight": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "rgbd_dsam_bwd_weight_multi": (_I, [_I, _P, _P, _P]),
+    "rgbd_point_sample": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "rgbd_point_sample_sets": (_I, [_I, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "rgbd_topk_rows_max_n": (_SZ, []),
     "rgbd_topk_rows": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -149,9 +138,7 @@ SIGNATURES = {
     "rgbd_ratio_feat_offset": (_SZ, [_I, _I, _I, _I]),
     "rgbd_ratio_hidden_offset": (_SZ, [_I, _I, _I, _I]),
     "rgbd_ratio_forward": (_I, [_I, _I, ctypes.c_float, _P, _LL, _I, _I, _I, _P, _P, ctypes.c_ulonglong, _P, _P,
-                                _P, _P]),
-    "rgbd_ratio_forward_ex": (_I, [_I, _I, ctypes.c_float, _P, _LL, _I, _I, _I, _P, _P, ctypes.c_ulonglong, _P, _P,
-                                   _P, _I, _P]),
+                                _P, _I, _P]),
 }
 
 # the diagnostic build's extra entry points (include/rgbd_hip_diag.h; librgbd_hip_diag.so via
@@ -161,7 +148,6 @@ DIAG_SIGNATURES = {
     "rgbd_debug_chain_stamps": (_I, [_P]),
     "rgbd_debug_dsam_stamps": (_I, [_P, _I]),
     "rgbd_debug_stem_lag_stamps": (_I, [_P]),
-    "rgbd_debug_conv5_mode": (_I, [_I]),
     "rgbd_debug_dsam_mode": (_I, [_I]),
 }
 

@@ -832,19 +832,11 @@ size_t rgbd_dggm_fuse_bwd_multi_workspace_size(int n, const int* C_host, const i
   return tot;
 }
 
-int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, const void* const* color_host,
-                             void* const* out_host, const float* const* weight_host, const float* const* bias_host,
-                             const int* C_host, const int* h_host, const int* w_host, const float* grad,
-                             const float* mask, long long pv_batch_stride, int B, int H, int W, void* stream) {
-  return rgbd_dggm_fuse_fwd_multi_mixed(dtype, n, cp1_host, 0, color_host, out_host, weight_host, bias_host, C_host,
-                                        h_host, w_host, grad, mask, pv_batch_stride, B, H, W, stream);
-}
-
-int rgbd_dggm_fuse_fwd_multi_mixed(int dtype, int n, const void* const* cp1_host, int cp1_nhwc_mask,
-                                   const void* const* color_host, void* const* out_host,
-                                   const float* const* weight_host, const float* const* bias_host, const int* C_host,
-                                   const int* h_host, const int* w_host, const float* grad, const float* mask,
-                                   long long pv_batch_stride, int B, int H, int W, void* stream) {
+int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, int cp1_nhwc_mask,
+                             const void* const* color_host, void* const* out_host, const float* const* weight_host,
+                             const float* const* bias_host, const int* C_host, const int* h_host, const int* w_host,
+                             const float* grad, const float* mask, long long pv_batch_stride, int B, int H, int W,
+                             void* stream) {
   RGBD_REQUIRE(grad && mask && color_host && out_host && weight_host && bias_host && B > 0 && H > 0 && W > 0,
                RGBD_E_ARG);
   DggmMulti m;

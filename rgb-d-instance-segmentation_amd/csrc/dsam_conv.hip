@@ -42,7 +42,8 @@ struct ConvArgs {
   const void* residual_nhwc;        // bf16 only: NHWC residual, used when out_nchw is null
   void* out_nchw;                   // optional
   void* out_nhwc;                   // optional
-  int ksplit;                       // unused (1)
+  int linear;                       // bf16: tile rows = 128 consecutive pixels of the (class) grid
+                                    // over the batch instead of 8 x 16 blocks (small grids)
   uint16_t* tmasks;                 // bf16: [class][tile][16] per-tap code sets (k_dsam_plan)
   int* items;                       // bf16: work list of k_dsam_lds (k_dsam_items)
   int* nitems;
@@ -51,8 +52,6 @@ struct ConvArgs {
   int ntiles0;                      // bf16: tiles of the largest class
   int chunk_len;                    // bf16: steps per workgroup chunk of a tile
   int ncg;                          // bf16: K chunk groups per tap (C / (32 * KC))
-  int linear;                       // bf16: tile rows = 128 consecutive pixels of the (class) grid
-                                    // over the batch instead of 8 x 16 blocks (small grids)
   float* partial;                   // bf16: partial tiles of multi-chunk tiles (reduced by their last chunk)
   const bf16_t* zero;               // bf16: LD_ZERO_BYTES of zeros (zeroed by k_dsam_plan)
   unsigned long long* stamps;       // diagnostics only (rgbd_debug_dsam_stamps); null otherwise
@@ -2019,10 +2018,6 @@ LdPlan ld_plan(const ConvArgs& a) {
   return p;
 }
 size_t ld_plan_bytes(const LdPlan& p) { return p.tmask_bytes + p.items_bytes + p.ticket_bytes; }
-size_t v2_partial_bytes(const ConvArgs& a) {
-  const LdPlan p = ld_plan(a);
-  return ld_plan_bytes(p) + p.partial_bytes;
-}
 // The bf16 launch arguments of a conv leg over its plan buffer [code sets | work list | tickets,
 // counters, zero row] (ld_plan_bytes) and its partial-tile buffer (P.partial_bytes).
 ConvArgs conv_carve(const ConvArgs& a, const LdPlan& P, char* plan, float* partial) {
@@ -2118,23 +2113,16 @@ hipError_t launch_ld_f32io(const ConvArgs& b, dim3 grid, hipStream_t s) {
   return hipSuccess;
 }
 
+// One conv leg (forward or dX).  bf16: the code-merged persistent kernel over the leg's plan
+// (rgbd_dsam_plan) and its partial-tile buffer a.partial; float32: the segment-form implicit
+// GEMM, no plan.
 template <typename T>
-int launch_conv(const ConvArgs& a, hipStream_t s, const void* planned = nullptr) {
+int launch_conv(const ConvArgs& a, hipStream_t s, const void* plan) {
   TimerScope ts(a.transposed ? "dsam_dx" : "dsam_fwd", s);
-  int nclass = a.transposed ? 4 : 1;
-  const long long Mmax = conv_mmax(a);
   if constexpr (sizeof(T) == 2) {
-    // code-merged bf16 path: the plan (unless the caller planned this leg ahead with
-    // rgbd_dsam_plan) into the head of the workspace, then the persistent kernel
     const LdPlan P = ld_plan(a);
     RGBD_REQUIRE(conv_shape_ok(a, P), RGBD_E_SHAPE);
-    char* plan = planned ? (char*)planned : (char*)a.partial;
-    float* partial = planned ? a.partial : (float*)((char*)a.partial + ld_plan_bytes(P));
-    const ConvArgs b = conv_carve(a, P, plan, partial);
-    if (!planned) {
-      const hipError_t pe = plan_convs(1, &b, s);
-      if (pe != hipSuccess) return (int)pe;
-    }
+    const ConvArgs b = conv_carve(a, P, (char*)plan, a.partial);
     // persistent: about one workgroup per CU (LDS-bound) over all N tiles
     constexpr int pers = 256;  // persistent: one LDS-bound workgroup per CU
     dim3 grid2(std::max(1, pers / P.ntn), P.ntn, 1);
@@ -2143,11 +2131,10 @@ int launch_conv(const ConvArgs& a, hipStream_t s, const void* planned = nullptr)
         f32io ? (P.kc == 3 ? launch_ld_f32io<3>(b, grid2, s) : P.kc == 2 ? launch_ld_f32io<2>(b, grid2, s) : launch_ld_f32io<1>(b, grid2, s))
               : (P.kc == 3 ? launch_ld<3>(b, grid2, s) : P.kc == 2 ? launch_ld<2>(b, grid2, s) : launch_ld<1>(b, grid2, s));
     if (e != hipSuccess) return (int)e;
-    RGBD_CHECK_LAUNCH();
-    return RGBD_OK;
+  } else {
+    dim3 grid(ceil_div(conv_mmax(a), BM), ceil_div(a.N, BN), a.transposed ? 4 : 1);
+    k_conv_igemm<T><<<grid, 256, 0, s>>>(a);
   }
-  dim3 grid(ceil_div(Mmax, BM), ceil_div(a.N, BN), nclass);
-  k_conv_igemm<T><<<grid, 256, 0, s>>>(a);
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }
@@ -2343,7 +2330,7 @@ static ConvArgs fwd_args(int B, int Cin, int h, int w, int Cout) {
   a.B = B; a.Hi = h; a.Wi = w; a.C = Cin;
   a.Ho = (h + 1) / 2; a.Wo = (w + 1) / 2; a.N = Cout;
   a.KH = 3; a.KW = 3; a.stride = 2; a.pad = 1;
-  a.nseg = 5; a.mask_mode = MASK_SRC; a.transposed = 0; a.ksplit = 1;
+  a.nseg = 5; a.mask_mode = MASK_SRC; a.transposed = 0;
   return a;
 }
 static ConvArgs dx_args(int B, int Cin, int h, int w, int Cout) {
@@ -2351,19 +2338,15 @@ static ConvArgs dx_args(int B, int Cin, int h, int w, int Cout) {
   a.B = B; a.Hi = (h + 1) / 2; a.Wi = (w + 1) / 2; a.C = Cout;
   a.Ho = h; a.Wo = w; a.N = Cin;
   a.KH = 3; a.KW = 3; a.stride = 2; a.pad = 1;
-  a.nseg = 5; a.mask_mode = MASK_DST; a.transposed = 1; a.ksplit = 1;
+  a.nseg = 5; a.mask_mode = MASK_DST; a.transposed = 1;
   return a;
-}
-
-size_t rgbd_dsam_conv_workspace_size(int dtype, int B, int Cin, int h, int w, int Cout) {
-  if (dtype != RGBD_BF16 || B <= 0 || h <= 0 || w <= 0) return 256;
-  const ConvArgs f = fwd_args(B, Cin, h, w, Cout), d = dx_args(B, Cin, h, w, Cout);
-  return std::max<size_t>(256, std::max(v2_partial_bytes(f), v2_partial_bytes(d)));
 }
 
 int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
                   int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                  const void* residual, void* out_nchw, void* out_nhwc, void* ws, void* stream) {
+                  const void* residual, void* out_nchw, void* out_nhwc, const void* plan, void* ws,
+                  void* stream) {
+  RGBD_REQUIRE(!plan || dtype == RGBD_BF16, RGBD_E_DTYPE);
   RGBD_REQUIRE(x_nhwc && code && info && wfwd && bias && (out_nchw || out_nhwc), RGBD_E_ARG);
   RGBD_REQUIRE(B > 0 && h > 0 && w > 0 && Cout > 0 && Cin > 0, RGBD_E_ARG);
   RGBD_REQUIRE(Cin % 8 == 0, RGBD_E_SHAPE);
@@ -2371,19 +2354,19 @@ int rgbd_dsam_fwd(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd
   a.x = x_nhwc; a.code = code; a.w = wfwd;
   a.bias4 = bias; a.info = info; a.residual = residual; a.out_nchw = out_nchw; a.out_nhwc = out_nhwc;
   a.partial = (float*)ws;
-  RGBD_REQUIRE(ws || dtype != RGBD_BF16, RGBD_E_ARG);
+  RGBD_REQUIRE((plan && ws) || dtype != RGBD_BF16, RGBD_E_ARG);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == RGBD_F32) return launch_conv<float>(a, s);
-  if (dtype == RGBD_BF16) return launch_conv<bf16_t>(a, s);
+  if (dtype == RGBD_F32) return launch_conv<float>(a, s, nullptr);
+  if (dtype == RGBD_BF16) return launch_conv<bf16_t>(a, s, plan);
   return RGBD_E_DTYPE;
 }
 
-static int fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info, int B,
-                    int Cin, int h, int w, int Cout, const void* wfwd, const float* bias, const void* residual_nhwc,
-                    void* out_nhwc, const void* planned, void* ws, void* stream,
-                    const float* residual_f32_nhwc = nullptr, float* out_f32_nhwc = nullptr) {
+int rgbd_dsam_fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info, int B,
+                       int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
+                       const void* residual_nhwc, void* out_nhwc, const float* residual_f32_nhwc,
+                       float* out_f32_nhwc, const void* plan, void* ws, void* stream) {
   RGBD_REQUIRE(dtype == RGBD_BF16, RGBD_E_DTYPE);
-  RGBD_REQUIRE(x_nhwc && code && info && wfwd && bias && (out_nhwc || out_f32_nhwc) && ws, RGBD_E_ARG);
+  RGBD_REQUIRE(x_nhwc && code && info && wfwd && bias && (out_nhwc || out_f32_nhwc) && plan && ws, RGBD_E_ARG);
   RGBD_REQUIRE(B > 0 && h > 0 && w > 0 && Cout > 0 && Cin > 0, RGBD_E_ARG);
   // the float32-interface kernel takes its residual as float32 only
   RGBD_REQUIRE(!((residual_f32_nhwc || out_f32_nhwc) && residual_nhwc), RGBD_E_ARG);
@@ -2393,44 +2376,13 @@ static int fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rg
   a.bias4 = bias; a.info = info; a.residual_nhwc = residual_nhwc; a.out_nhwc = out_nhwc;
   a.residual_f32_nhwc = residual_f32_nhwc; a.out_f32_nhwc = out_f32_nhwc;
   a.partial = (float*)ws;
-  return launch_conv<bf16_t>(a, (hipStream_t)stream, planned);
-}
-int rgbd_dsam_fwd_nhwc(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                       int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                       const void* residual_nhwc, void* out_nhwc, void* ws, void* stream) {
-  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, nullptr, ws,
-                  stream);
-}
-int rgbd_dsam_fwd_nhwc_planned(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                               int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                               const void* residual_nhwc, void* out_nhwc, const void* plan, void* ws, void* stream) {
-  RGBD_REQUIRE(plan, RGBD_E_ARG);
-  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, plan, ws,
-                  stream);
+  return launch_conv<bf16_t>(a, (hipStream_t)stream, plan);
 }
 
-int rgbd_dsam_fwd_nhwc_f32io(int dtype, const void* x_nhwc, const uint8_t* code, const rgbd_decomp_info* info,
-                             int B, int Cin, int h, int w, int Cout, const void* wfwd, const float* bias,
-                             const void* residual_nhwc, void* out_nhwc, void* ws, void* stream,
-                             const float* residual_f32_nhwc, float* out_f32_nhwc) {
-  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, nullptr, ws,
-                  stream, residual_f32_nhwc, out_f32_nhwc);
-}
-int rgbd_dsam_fwd_nhwc_f32io_planned(int dtype, const void* x_nhwc, const uint8_t* code,
-                                     const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
-                                     const void* wfwd, const float* bias, const void* residual_nhwc, void* out_nhwc,
-                                     const void* plan, void* ws, void* stream, const float* residual_f32_nhwc,
-                                     float* out_f32_nhwc) {
-  RGBD_REQUIRE(dtype == RGBD_BF16, RGBD_E_DTYPE);
-  RGBD_REQUIRE(plan, RGBD_E_ARG);
-  return fwd_nhwc(dtype, x_nhwc, code, info, B, Cin, h, w, Cout, wfwd, bias, residual_nhwc, out_nhwc, plan, ws,
-                  stream, residual_f32_nhwc, out_f32_nhwc);
-}
-
-static int bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h, int w, int Cout,
-                    const void* wbwd, const void* gin_nchw, const void* gin_nhwc, void* dx_nchw, void* dx_nhwc,
-                    const void* planned, void* ws, void* stream) {
-  RGBD_REQUIRE(!planned || dtype == RGBD_BF16, RGBD_E_DTYPE);
+int rgbd_dsam_bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h, int w,
+                       int Cout, const void* wbwd, const void* gin_nchw, const void* gin_nhwc, void* dx_nchw,
+                       void* dx_nhwc, const void* plan, void* ws, void* stream) {
+  RGBD_REQUIRE(!plan || dtype == RGBD_BF16, RGBD_E_DTYPE);
   RGBD_REQUIRE(gout_nhwc && code && wbwd && (dx_nchw || dx_nhwc), RGBD_E_ARG);
   // the residual comes in the layout of the pass that adds it: NCHW with an NCHW output, NHWC
   // (bf16 only) without one
@@ -2442,71 +2394,55 @@ static int bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B
   a.x = gout_nhwc; a.code = code; a.w = wbwd;
   a.residual = gin_nchw; a.residual_nhwc = gin_nhwc; a.out_nchw = dx_nchw; a.out_nhwc = dx_nhwc;
   a.partial = (float*)ws;
-  RGBD_REQUIRE(ws || dtype != RGBD_BF16, RGBD_E_ARG);
+  RGBD_REQUIRE((plan && ws) || dtype != RGBD_BF16, RGBD_E_ARG);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == RGBD_F32) return launch_conv<float>(a, s);
-  if (dtype == RGBD_BF16) return launch_conv<bf16_t>(a, s, planned);
+  if (dtype == RGBD_F32) return launch_conv<float>(a, s, nullptr);
+  if (dtype == RGBD_BF16) return launch_conv<bf16_t>(a, s, plan);
   return RGBD_E_DTYPE;
 }
-int rgbd_dsam_bwd_data(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h,
-                       int w, int Cout, const void* wbwd, const void* gin_nchw, const void* gin_nhwc,
-                       void* dx_nchw, void* dx_nhwc, void* ws, void* stream) {
-  return bwd_data(dtype, gout_nhwc, code, B, Cin, h, w, Cout, wbwd, gin_nchw, gin_nhwc, dx_nchw, dx_nhwc, nullptr, ws,
-                  stream);
-}
-int rgbd_dsam_bwd_data_planned(int dtype, const void* gout_nhwc, const uint8_t* code, int B, int Cin, int h,
-                               int w, int Cout, const void* wbwd, const void* gin_nchw, const void* gin_nhwc,
-                               void* dx_nchw, void* dx_nhwc, const void* plan, void* ws, void* stream) {
-  RGBD_REQUIRE(plan, RGBD_E_ARG);
-  return bwd_data(dtype, gout_nhwc, code, B, Cin, h, w, Cout, wbwd, gin_nchw, gin_nhwc, dx_nchw, dx_nhwc, plan, ws,
-                  stream);
-}
 
-// bf16 workspace: the plan part [presence table [B][units] u16 | live entry list | their tap
-// masks | items | counters | zero row] (plan_total bytes; rgbd_dsam_plan can fill it ahead),
-// then [items][Cout][9 Cin] f32 partials | channel sums
-struct WgradWs {
-  size_t pres, gmask, list, masks, items, counts, zero, plan_total, partial, csum, total;
+// bf16 dW plan (rgbd_dsam_plan_size(RGBD_LEG_DW) = total): [presence table [B][units] u16 | 256
+// spare bytes | live entry list | their tap masks | items | counters | zero row]
+struct WgPlanWs {
+  size_t pres, list, masks, items, counts, zero, total;
 };
-static WgradWs wgrad_ws(int dtype, int B, int Cin, int h, int w, int Cout) {
-  WgradWs o;
+static WgPlanWs wg_plan_ws(const WgPlan& p, int B) {
+  WgPlanWs o;
   size_t off = 0;
-  size_t part, npres = 1, nent = 1, nitems = 1;
-  if (dtype == RGBD_BF16) {
-    const WgPlan p = wg_plan(B, Cin, h, w, Cout);
-    nitems = wg_max_items(p);
-    part = nitems * Cout * 9 * Cin;
-    npres = (size_t)B * p.nunit;
-    nent = p.max_entries;
-  } else {
-    part = (size_t)dsam_wgrad_splits(B, Cin, Cout) * Cout * 45 * Cin;
-  }
   o.pres = off;
-  off += align256(sizeof(uint16_t) * npres);
-  o.gmask = off;
-  off += 256;
+  off += align256(sizeof(uint16_t) * (size_t)B * p.nunit) + 256;
   o.list = off;
-  off += align256(sizeof(int) * nent);
+  off += align256(sizeof(int) * (size_t)p.max_entries);
   o.masks = off;
-  off += align256(sizeof(unsigned long long) * 9 * nent);
+  off += align256(sizeof(unsigned long long) * 9 * p.max_entries);
   o.items = off;
-  off += align256(sizeof(int4) * nitems);
+  off += align256(sizeof(int4) * wg_max_items(p));
   o.counts = off;
   off += 256;
   o.zero = off;
   off += LD_ZERO_BYTES;
-  o.plan_total = off;
-  o.partial = off;
-  off += align256(sizeof(float) * part);
-  o.csum = off;
-  off += align256(sizeof(float) * (size_t)CS_SPLIT_MAX * B * Cout);
   o.total = off;
   return o;
 }
+// dW run workspace: [partials f32 (bf16: [items][Cout][9 Cin]; float32: [splits][Cout][45 Cin]) |
+// channel sums]
+struct WgRunWs {
+  size_t csum, total;  // the partials start the workspace
+};
+static WgRunWs wg_run_ws(int dtype, int B, int Cin, int h, int w, int Cout) {
+  const size_t part = dtype == RGBD_BF16 ? wg_max_items(wg_plan(B, Cin, h, w, Cout)) * Cout * 9 * Cin
+                                         : (size_t)dsam_wgrad_splits(B, Cin, Cout) * Cout * 45 * Cin;
+  WgRunWs o;
+  o.csum = align256(sizeof(float) * part);
+  o.total = o.csum + align256(sizeof(float) * (size_t)CS_SPLIT_MAX * B * Cout);
+  return o;
+}
 
-// dW launch arguments over a plan part (wgrad_ws offsets below plan_total) and the partials
-static WgArgs wg_args(const WgradWs& L, const WgPlan& P, char* plan, float* partial, const void* gout_nhwc,
-                      const void* x_nhwc, const uint8_t* code, int B, int Cin, int h, int w, int Cout) {
+// dW launch arguments of a bf16 leg over its plan and its run workspace (the partials): both NULL
+// with the data pointers when only planning (rgbd_dsam_plan)
+static WgArgs wg_args(const WgPlan& P, char* plan, void* ws, const void* gout_nhwc, const void* x_nhwc,
+                      const uint8_t* code, int B, int Cin, int h, int w, int Cout) {
+  const WgPlanWs L = wg_plan_ws(P, B);
   WgArgs a;
   a.gout = (const bf16_t*)gout_nhwc;
   a.x = (const bf16_t*)x_nhwc;
@@ -2524,7 +2460,7 @@ static WgArgs wg_args(const WgradWs& L, const WgPlan& P, char* plan, float* part
   a.target = wg_target(P);
   a.inv_wo = 1.0f / (float)a.wo;
   a.zero = (const bf16_t*)(plan + L.zero);
-  a.partial = partial;
+  a.partial = (float*)ws;
   return a;
 }
 static bool wg_shape_ok(int B, int Cin, int h, int w, int Cout, const WgPlan& P) {
@@ -2549,9 +2485,21 @@ static void wg_plan_launch(int n, const WgArgs* a, const WgPlan* P, hipStream_t 
   k_wg_masks_legs<<<dim3((unsigned)mask_blocks, 1, n), 256, 0, s>>>(L);
 }
 
-size_t rgbd_dsam_bwd_weight_workspace_size(int dtype, int B, int Cin, int h, int w, int Cout) {
-  if (B <= 0 || h <= 0 || w <= 0 || Cin <= 0 || Cout <= 0) return 256;
-  return wgrad_ws(dtype, B, Cin, h, w, Cout).total;
+// a bf16 dW leg ready to run: its launch arguments over (plan, run workspace), the channel-sum
+// buffer in that workspace and the output tile shape
+struct WgRun {
+  WgArgs a;
+  float* csum;
+  int fm;
+};
+static int wg_run(WgRun& r, const void* gout_nhwc, const void* x_nhwc, const uint8_t* code, int B, int Cin, int h,
+                  int w, int Cout, const void* plan, void* ws) {
+  const WgPlan P = wg_plan(B, Cin, h, w, Cout);
+  RGBD_REQUIRE(wg_shape_ok(B, Cin, h, w, Cout, P), RGBD_E_SHAPE);
+  r.a = wg_args(P, (char*)plan, ws, gout_nhwc, x_nhwc, code, B, Cin, h, w, Cout);
+  r.csum = (float*)((char*)ws + wg_run_ws(RGBD_BF16, B, Cin, h, w, Cout).csum);
+  r.fm = P.fm;
+  return RGBD_OK;
 }
 
 static CombArgs comb_args(const WgArgs& a, bool nchw_sums, const float* csum, const rgbd_decomp_info* info,
@@ -2588,70 +2536,49 @@ static int wg_finish(const WgArgs& a, const void* gout_nchw, float* csum, const 
   return RGBD_OK;
 }
 
-static int bwd_weight(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
-                      const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h, int w, int Cout,
-                      float* dconv_w, float* dproj_w, float* dbias, const void* planned, void* ws, void* stream) {
+int rgbd_dsam_bwd_weight(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
+                         const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h, int w,
+                         int Cout, float* dconv_w, float* dproj_w, float* dbias, const void* plan, void* ws,
+                         void* stream) {
+  RGBD_REQUIRE(!plan || dtype == RGBD_BF16, RGBD_E_ARG);
   RGBD_REQUIRE((gout_nchw || dtype == RGBD_BF16) && x_nhwc && code && info && dconv_w && dproj_w && dbias && ws,
                RGBD_E_ARG);
   RGBD_REQUIRE(B > 0 && h > 0 && w > 0 && Cout > 0 && Cin > 0, RGBD_E_ARG);
   RGBD_REQUIRE(Cin % 8 == 0, RGBD_E_SHAPE);
   hipStream_t s = (hipStream_t)stream;
-  const WgradWs L = wgrad_ws(dtype, B, Cin, h, w, Cout);
-  // planned ahead: ws holds only [partials | channel sums]
-  const size_t run0 = planned ? L.plan_total : 0;
-  float* partial = (float*)((char*)ws + L.partial - run0);
-  float* csum = (float*)((char*)ws + L.csum - run0);
   TimerScope ts("dsam_wgrad", s);
-  const int ho = (h + 1) / 2, wo = (w + 1) / 2, hwo = ho * wo;
-  if (dtype == RGBD_F32) {
-    const int sp = dsam_wgrad_splits(B, Cin, Cout);
-    dim3 grid(ceil_div(45ll * Cin, 64), ceil_div(Cout, 64), sp);
-    k_dsam_wgrad<float><<<grid, 256, 0, s>>>((const float*)gout_nchw, (const float*)x_nhwc, code, B, Cin, h, w,
-                                             Cout, sp, partial);
-    k_chan_sum<float><<<B * Cout, 256, 0, s>>>((const float*)gout_nchw, hwo, csum);
-    const long long total = 45ll * Cin * Cout;
-    k_dsam_wgrad_final<<<(int)std::min<long long>(ceil_div(total, 256), 4096), 256, 0, s>>>(
-        partial, sp, Cin, Cout, dconv_w, dproj_w);
-  } else if (dtype == RGBD_BF16) {
-    RGBD_REQUIRE(gout_nhwc, RGBD_E_ARG);
-    const WgPlan P = wg_plan(B, Cin, h, w, Cout);
-    RGBD_REQUIRE(wg_shape_ok(B, Cin, h, w, Cout, P), RGBD_E_SHAPE);
-    char* plan = planned ? (char*)planned : (char*)ws;
+  if (dtype == RGBD_BF16) {
+    RGBD_REQUIRE(gout_nhwc && plan, RGBD_E_ARG);
+    WgRun r;
+    const int rc = wg_run(r, gout_nhwc, x_nhwc, code, B, Cin, h, w, Cout, plan, ws);
+    if (rc != RGBD_OK) return rc;
     WgMulti<1> m;
-    m.a[0] = wg_args(L, P, plan, partial, gout_nhwc, x_nhwc, code, B, Cin, h, w, Cout);
+    m.a[0] = r.a;
     m.n = 1;
-    m.csum[0] = csum;
+    m.csum[0] = r.csum;
     m.fold = gout_nchw == nullptr;  // NHWC bias sums drained by the GEMM's workgroups
-    if (!planned) wg_plan_launch(1, &m.a[0], &P, s);
-    const hipError_t e = launch_wg_fm(P.fm, m, s);
+    const hipError_t e = launch_wg_fm(r.fm, m, s);
     if (e != hipSuccess) return (int)e;
-    return wg_finish(m.a[0], gout_nchw, csum, info, dconv_w, dproj_w, dbias, s, m.fold);
-  } else {
-    return RGBD_E_DTYPE;
+    return wg_finish(r.a, gout_nchw, r.csum, info, dconv_w, dproj_w, dbias, s, m.fold);
   }
-  const int nsplit = (dtype == RGBD_BF16 && !gout_nchw) ? chan_sum_splits(hwo) : 1;
-  k_dsam_bias_grad<<<Cout, 256, 0, s>>>(csum, info, B, Cout, nsplit, dbias);
+  if (dtype != RGBD_F32) return RGBD_E_DTYPE;
+  float* partial = (float*)ws;
+  float* csum = (float*)((char*)ws + wg_run_ws(RGBD_F32, B, Cin, h, w, Cout).csum);
+  const int hwo = ((h + 1) / 2) * ((w + 1) / 2);
+  const int sp = dsam_wgrad_splits(B, Cin, Cout);
+  dim3 grid(ceil_div(45ll * Cin, 64), ceil_div(Cout, 64), sp);
+  k_dsam_wgrad<float><<<grid, 256, 0, s>>>((const float*)gout_nchw, (const float*)x_nhwc, code, B, Cin, h, w, Cout,
+                                           sp, partial);
+  k_chan_sum<float><<<B * Cout, 256, 0, s>>>((const float*)gout_nchw, hwo, csum);
+  const long long total = 45ll * Cin * Cout;
+  k_dsam_wgrad_final<<<(int)std::min<long long>(ceil_div(total, 256), 4096), 256, 0, s>>>(
+      partial, sp, Cin, Cout, dconv_w, dproj_w);
+  k_dsam_bias_grad<<<Cout, 256, 0, s>>>(csum, info, B, Cout, 1, dbias);
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }
 
-int rgbd_dsam_bwd_weight(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
-                         const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h, int w,
-                         int Cout, float* dconv_w, float* dproj_w, float* dbias, void* ws, void* stream) {
-  return bwd_weight(dtype, gout_nchw, gout_nhwc, x_nhwc, code, info, B, Cin, h, w, Cout, dconv_w, dproj_w, dbias,
-                    nullptr, ws, stream);
-}
-int rgbd_dsam_bwd_weight_planned(int dtype, const void* gout_nchw, const void* gout_nhwc, const void* x_nhwc,
-                                 const uint8_t* code, const rgbd_decomp_info* info, int B, int Cin, int h, int w,
-                                 int Cout, float* dconv_w, float* dproj_w, float* dbias, const void* plan, void* ws,
-                                 void* stream) {
-  RGBD_REQUIRE(plan && dtype == RGBD_BF16, RGBD_E_ARG);
-  return bwd_weight(dtype, gout_nchw, gout_nhwc, x_nhwc, code, info, B, Cin, h, w, Cout, dconv_w, dproj_w, dbias,
-                    plan, ws, stream);
-}
-
-int rgbd_dsam_bwd_weight_planned_multi(int n, const rgbd_dsam_dw_run* runs, const rgbd_decomp_info* info,
-                                       void* stream) {
+int rgbd_dsam_bwd_weight_multi(int n, const rgbd_dsam_dw_run* runs, const rgbd_decomp_info* info, void* stream) {
   RGBD_REQUIRE(n >= 1 && n <= 2 && runs && info, RGBD_E_ARG);
   hipStream_t s = (hipStream_t)stream;
   TimerScope ts("dsam_wgrad", s);
@@ -2662,13 +2589,12 @@ int rgbd_dsam_bwd_weight_planned_multi(int n, const rgbd_dsam_dw_run* runs, cons
     const rgbd_dsam_dw_run& r = runs[i];
     RGBD_REQUIRE(r.gout_nhwc && r.x_nhwc && r.code && r.dconv_w && r.dproj_w && r.dbias && r.plan && r.ws, RGBD_E_ARG);
     RGBD_REQUIRE(r.B > 0 && r.h > 0 && r.w > 0 && r.Cout > 0 && r.Cin > 0 && r.Cin % 8 == 0, RGBD_E_SHAPE);
-    const WgradWs L = wgrad_ws(RGBD_BF16, r.B, r.Cin, r.h, r.w, r.Cout);
-    const WgPlan P = wg_plan(r.B, r.Cin, r.h, r.w, r.Cout);
-    RGBD_REQUIRE(wg_shape_ok(r.B, r.Cin, r.h, r.w, r.Cout, P), RGBD_E_SHAPE);
-    float* partial = (float*)((char*)r.ws + L.partial - L.plan_total);
-    m.a[i] = wg_args(L, P, (char*)r.plan, partial, r.gout_nhwc, r.x_nhwc, r.code, r.B, r.Cin, r.h, r.w, r.Cout);
-    m.csum[i] = (float*)((char*)r.ws + L.csum - L.plan_total);
-    fm[i] = P.fm;
+    WgRun g;
+    const int rc = wg_run(g, r.gout_nhwc, r.x_nhwc, r.code, r.B, r.Cin, r.h, r.w, r.Cout, r.plan, r.ws);
+    if (rc != RGBD_OK) return rc;
+    m.a[i] = g.a;
+    m.csum[i] = g.csum;
+    fm[i] = g.fm;
   }
   for (int i = 0; i + 1 < n; ++i)  // distinct buffers: the legs run together
     RGBD_REQUIRE(runs[i].ws != runs[i + 1].ws && runs[i].plan != runs[i + 1].plan, RGBD_E_ARG);
@@ -2716,16 +2642,14 @@ static bool leg_ok(const rgbd_dsam_leg& g) {
 size_t rgbd_dsam_plan_size(int kind, int B, int Cin, int h, int w, int Cout) {
   const rgbd_dsam_leg g = {kind, nullptr, B, Cin, h, w, Cout, nullptr};
   if (!leg_ok(g)) return 0;
-  if (kind == RGBD_LEG_DW) return wgrad_ws(RGBD_BF16, B, Cin, h, w, Cout).plan_total;
+  if (kind == RGBD_LEG_DW) return wg_plan_ws(wg_plan(B, Cin, h, w, Cout), B).total;
   return ld_plan_bytes(ld_plan(leg_conv_args(g)));
 }
-size_t rgbd_dsam_run_workspace_size(int kind, int B, int Cin, int h, int w, int Cout) {
+size_t rgbd_dsam_run_workspace_size(int dtype, int kind, int B, int Cin, int h, int w, int Cout) {
   const rgbd_dsam_leg g = {kind, nullptr, B, Cin, h, w, Cout, nullptr};
-  if (!leg_ok(g)) return 0;
-  if (kind == RGBD_LEG_DW) {
-    const WgradWs L = wgrad_ws(RGBD_BF16, B, Cin, h, w, Cout);
-    return L.total - L.plan_total;
-  }
+  if (!leg_ok(g) || (dtype != RGBD_BF16 && dtype != RGBD_F32)) return 0;
+  if (kind == RGBD_LEG_DW) return wg_run_ws(dtype, B, Cin, h, w, Cout).total;
+  if (dtype == RGBD_F32) return 256;  // the float32 forward / dX use no workspace
   return std::max<size_t>(256, ld_plan(leg_conv_args(g)).partial_bytes);
 }
 #ifdef RGBD_DIAG
@@ -2759,9 +2683,8 @@ int rgbd_dsam_plan(int n, const rgbd_dsam_leg* legs, void* stream) {
       RGBD_REQUIRE(nwg < WG_MAXLEG, RGBD_E_ARG);
       const WgPlan P = wg_plan(g.B, g.Cin, g.h, g.w, g.Cout);
       RGBD_REQUIRE(wg_shape_ok(g.B, g.Cin, g.h, g.w, g.Cout, P), RGBD_E_SHAPE);
-      const WgradWs L = wgrad_ws(RGBD_BF16, g.B, g.Cin, g.h, g.w, g.Cout);
       wgp[nwg] = P;
-      wga[nwg++] = wg_args(L, P, (char*)g.plan, nullptr, nullptr, nullptr, g.code, g.B, g.Cin, g.h, g.w, g.Cout);
+      wga[nwg++] = wg_args(P, (char*)g.plan, nullptr, nullptr, nullptr, g.code, g.B, g.Cin, g.h, g.w, g.Cout);
       continue;
     }
     RGBD_REQUIRE(nconv < PLAN_MAXLEG, RGBD_E_ARG);

@@ -354,30 +354,21 @@ __global__ __launch_bounds__(TK_THR) void k_topk_rows(const float* __restrict__ 
 
 extern "C" {
 
-int rgbd_point_sample(const float* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord, int P,
-                      float* out, void* stream) {
+int rgbd_point_sample(int dtype, const void* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord,
+                      int P, float* out, void* stream) {
+  RGBD_REQUIRE(dtype == RGBD_F32 || dtype == RGBD_BF16, RGBD_E_DTYPE);
   // nothing to sample (empty tensors carry null data pointers): checked before the pointers
   RGBD_REQUIRE(nmaps >= 0 && h > 0 && w > 0 && P >= 0 && maps_per_coord > 0, RGBD_E_ARG);
   const long long n = (long long)nmaps * P;
   if (n == 0) return RGBD_OK;
   RGBD_REQUIRE(maps && coords && out, RGBD_E_ARG);
-  k_point_sample<float><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(maps, nmaps, h, w, coords,
-                                                                                      maps_per_coord, nullptr, P, out);
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-int rgbd_point_sample_t(int dtype, const void* maps, int nmaps, int h, int w, const float* coords, int maps_per_coord,
-                        int P, float* out, void* stream) {
+  const unsigned grid = (unsigned)((n + 255) / 256);
   if (dtype == RGBD_F32)
-    return rgbd_point_sample((const float*)maps, nmaps, h, w, coords, maps_per_coord, P, out, stream);
-  RGBD_REQUIRE(dtype == RGBD_BF16, RGBD_E_DTYPE);
-  RGBD_REQUIRE(nmaps >= 0 && h > 0 && w > 0 && P >= 0 && maps_per_coord > 0, RGBD_E_ARG);
-  const long long n = (long long)nmaps * P;
-  if (n == 0) return RGBD_OK;
-  RGBD_REQUIRE(maps && coords && out, RGBD_E_ARG);
-  k_point_sample<bf16_t><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      (const bf16_t*)maps, nmaps, h, w, coords, maps_per_coord, nullptr, P, out);
+    k_point_sample<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)maps, nmaps, h, w, coords,
+                                                                 maps_per_coord, nullptr, P, out);
+  else
+    k_point_sample<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_t*)maps, nmaps, h, w, coords,
+                                                                  maps_per_coord, nullptr, P, out);
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }

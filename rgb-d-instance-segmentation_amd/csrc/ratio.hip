@@ -2950,14 +2950,7 @@ size_t rgbd_ratio_workspace_size(int dtype, int B, int H, int W) {
 
 int rgbd_ratio_forward(int dtype, int training, float momentum, const float* depth3, long long batch_stride,
                        int B, int H, int W, const void* packed, float* const* bn_host, unsigned long long seed,
-                       unsigned long long* seed_counter, float* ratio, void* ws, void* stream) {
-  return rgbd_ratio_forward_ex(dtype, training, momentum, depth3, batch_stride, B, H, W, packed, bn_host, seed,
-                               seed_counter, ratio, ws, 0, stream);
-}
-
-int rgbd_ratio_forward_ex(int dtype, int training, float momentum, const float* depth3, long long batch_stride,
-                          int B, int H, int W, const void* packed, float* const* bn_host, unsigned long long seed,
-                          unsigned long long* seed_counter, float* ratio, void* ws, int flags, void* stream) {
+                       unsigned long long* seed_counter, float* ratio, void* ws, int flags, void* stream) {
   RGBD_REQUIRE((flags & ~RGBD_RATIO_F_PHASE2) == 0, RGBD_E_ARG);
   RGBD_REQUIRE(depth3 && packed && bn_host && ratio && ws, RGBD_E_ARG);
   RGBD_REQUIRE(B > 0 && H > 0 && W > 0, RGBD_E_ARG);

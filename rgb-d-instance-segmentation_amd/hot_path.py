@@ -54,7 +54,7 @@ def side_stream(dev):
     return s
 
 
-# bf16 backward: the dW GEMMs of dsam1 and dsam0 in one launch (rgbd_dsam_bwd_weight_planned_multi);
+# bf16 backward: the dW GEMMs of dsam1 and dsam0 in one launch (rgbd_dsam_bwd_weight_multi);
 # False runs them as two launches, dW1 on the side stream (bitwise the same gradients)
 JOINT_DW = True
 

@@ -400,7 +400,7 @@ def _ints(xs):
 
 
 def dggm_fuse_fwd_multi(cp1s, colors, pixel_values, weights, biases, cp1_nhwc=()):
-    """dggm_fuse_fwd for every scale in one launch (rgbd_dggm_fuse_fwd_multi[_mixed]); cp1s may be
+    """dggm_fuse_fwd for every scale in one launch (rgbd_dggm_fuse_fwd_multi); cp1s may be
     None; scales listed in ``cp1_nhwc`` take their cp1 as NHWC [B,h,w,C] (the DSAM cascade's
     output layout) instead of NCHW."""
     _need_cuda(*colors, pixel_values)
@@ -423,11 +423,11 @@ def dggm_fuse_fwd_multi(cp1s, colors, pixel_values, weights, biases, cp1_nhwc=()
     wts = [w.reshape(w.shape[0], 3).float().contiguous() for w in weights]
     bss = [b.float().contiguous() for b in biases]
     grad, gmask = _grad_mask(pixel_values)
-    check(_lib.lib().rgbd_dggm_fuse_fwd_multi_mixed(
+    check(_lib.lib().rgbd_dggm_fuse_fwd_multi(
         _dtype_code(colors[0]), n, None if cp1s is None else _ptrs(cp1s), cp1_mask, _ptrs(colors), _ptrs(outs),
         _ptrs(wts), _ptrs(bss), _ints([c.shape[1] for c in colors]), _ints([c.shape[2] for c in colors]),
         _ints([c.shape[3] for c in colors]), ctypes.c_void_p(grad.data_ptr()), ctypes.c_void_p(gmask.data_ptr()),
-        pixel_values.stride(0), B, H, W, _stream(pixel_values.device)), "rgbd_dggm_fuse_fwd_multi_mixed")
+        pixel_values.stride(0), B, H, W, _stream(pixel_values.device)), "rgbd_dggm_fuse_fwd_multi")
     return outs
 
 
@@ -584,6 +584,16 @@ def dsam_plan(legs):
     return plans
 
 
+def _dsam_leg(kind, code, ci, co, dt, plan, tag):
+    """(plan, run workspace) of one DSAM leg.  bfloat16 legs run from a plan: ``plan``, or one made
+    here for this leg alone (dsam_plan on the current stream); float32 legs have none."""
+    if dt == RGBD_BF16 and plan is None:
+        plan, = dsam_plan([(kind, code, ci, co)])
+    B, h, w = code.shape
+    ws = _workspace(code.device, _lib.lib().rgbd_dsam_run_workspace_size(dt, kind, B, ci, h, w, co), tag)
+    return plan, ws
+
+
 def dsam_fwd(x_nhwc, code, info, wfwd, bias4, residual=None, want_nhwc=False):
     """x_nhwc [B,h,w,Ci] -> (out_nchw [B,Co,ho,wo], out_nhwc or None)."""
     _need_cuda(x_nhwc, code, info, wfwd, bias4, residual)
@@ -597,12 +607,29 @@ def dsam_fwd(x_nhwc, code, info, wfwd, bias4, residual=None, want_nhwc=False):
     out = torch.empty((B, Co, ho, wo), dtype=x_nhwc.dtype, device=x_nhwc.device)
     out_nhwc = torch.empty((B, ho, wo, Co), dtype=x_nhwc.dtype, device=x_nhwc.device) if want_nhwc else None
     b4 = bias4.detach().float().contiguous()
-    L = _lib.lib()
     dt = _dtype_code(x_nhwc)
-    ws = _workspace(x_nhwc.device, L.rgbd_dsam_conv_workspace_size(dt, B, Ci, h, w, Co), "dsam_conv")
-    check(L.rgbd_dsam_fwd(dt, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4), _p(residual),
-                          _p(out), _p(out_nhwc), _p(ws), _stream(x_nhwc.device)), "rgbd_dsam_fwd")
+    plan, ws = _dsam_leg(LEG_FWD, code, Ci, Co, dt, None, "dsam_conv")
+    check(_lib.lib().rgbd_dsam_fwd(dt, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
+                                   _p(residual), _p(out), _p(out_nhwc), _p(plan), _p(ws),
+                                   _stream(x_nhwc.device)), "rgbd_dsam_fwd")
     return out, out_nhwc
+
+
+def _dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, residual_nhwc, residual_f32_nhwc, want_bf16, want_f32, plan):
+    """rgbd_dsam_fwd_nhwc behind dsam_fwd_nhwc and dsam_fwd_nhwc_f32io -> (out_bf16, out_f32)."""
+    B, h, w, Ci = x_nhwc.shape
+    Co = bias4.shape[-1]
+    ho, wo = (h + 1) // 2, (w + 1) // 2
+    if tuple(code.shape) != (B, h, w):
+        raise ValueError(f"region code {tuple(code.shape)} does not match features {(B, h, w)}")
+    out = torch.empty((B, ho, wo, Co), dtype=torch.bfloat16, device=x_nhwc.device) if want_bf16 else None
+    out32 = torch.empty((B, ho, wo, Co), dtype=torch.float32, device=x_nhwc.device) if want_f32 else None
+    b4 = bias4.detach().float().contiguous()
+    plan, ws = _dsam_leg(LEG_FWD, code, Ci, Co, RGBD_BF16, plan, "dsam_conv")
+    check(_lib.lib().rgbd_dsam_fwd_nhwc(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
+                                        _p(residual_nhwc), _p(out), _p(residual_f32_nhwc), _p(out32), _p(plan),
+                                        _p(ws), _stream(x_nhwc.device)), "rgbd_dsam_fwd_nhwc")
+    return out, out32
 
 
 def dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, residual_nhwc=None, plan=None):
@@ -611,31 +638,15 @@ def dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, residual_nhwc=None, plan=None
     _need_cuda(x_nhwc, code, info, wfwd, bias4, residual_nhwc, plan)
     if x_nhwc.dtype != torch.bfloat16:
         raise TypeError("dsam_fwd_nhwc is the bfloat16 path")
-    B, h, w, Ci = x_nhwc.shape
-    Co = bias4.shape[-1]
-    ho, wo = (h + 1) // 2, (w + 1) // 2
-    if tuple(code.shape) != (B, h, w):
-        raise ValueError(f"region code {tuple(code.shape)} does not match features {(B, h, w)}")
-    if residual_nhwc is not None and tuple(residual_nhwc.shape) != (B, ho, wo, Co):
-        raise ValueError(f"residual {tuple(residual_nhwc.shape)} != {(B, ho, wo, Co)}")
-    out = torch.empty((B, ho, wo, Co), dtype=x_nhwc.dtype, device=x_nhwc.device)
-    b4 = bias4.detach().float().contiguous()
-    L = _lib.lib()
-    if plan is not None:
-        ws = _workspace(x_nhwc.device, L.rgbd_dsam_run_workspace_size(LEG_FWD, B, Ci, h, w, Co), "dsam_conv")
-        check(L.rgbd_dsam_fwd_nhwc_planned(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd),
-                                           _p(b4), _p(residual_nhwc), _p(out), _p(plan), _p(ws),
-                                           _stream(x_nhwc.device)), "rgbd_dsam_fwd_nhwc_planned")
-        return out
-    ws = _workspace(x_nhwc.device, L.rgbd_dsam_conv_workspace_size(RGBD_BF16, B, Ci, h, w, Co), "dsam_conv")
-    check(L.rgbd_dsam_fwd_nhwc(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
-                               _p(residual_nhwc), _p(out), _p(ws), _stream(x_nhwc.device)), "rgbd_dsam_fwd_nhwc")
-    return out
+    exp = (x_nhwc.shape[0], (x_nhwc.shape[1] + 1) // 2, (x_nhwc.shape[2] + 1) // 2, bias4.shape[-1])
+    if residual_nhwc is not None and tuple(residual_nhwc.shape) != exp:
+        raise ValueError(f"residual {tuple(residual_nhwc.shape)} != {exp}")
+    return _dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, residual_nhwc, None, True, False, plan)[0]
 
 
 def dsam_fwd_nhwc_f32io(x_nhwc, code, info, wfwd, bias4, residual_f32_nhwc=None, want_bf16=True, want_f32=True,
                         plan=None):
-    """dsam_fwd_nhwc with a float32 interface (rgbd_dsam_fwd_nhwc_f32io[_planned]): bf16 operands,
+    """dsam_fwd_nhwc with a float32 interface (rgbd_dsam_fwd_nhwc's float32 pointers): bf16 operands,
     an optional float32 NHWC residual, -> (out_bf16, out_f32), both [B,ho,wo,Co]: out_f32 =
     residual + (acc + bias) in float32, out_bf16 its one rounding; ``want_bf16`` / ``want_f32``
     False leave that one out (None)."""
@@ -644,30 +655,11 @@ def dsam_fwd_nhwc_f32io(x_nhwc, code, info, wfwd, bias4, residual_f32_nhwc=None,
         raise TypeError("dsam_fwd_nhwc_f32io computes in bfloat16 (x_nhwc must be bfloat16)")
     if not (want_bf16 or want_f32):
         raise ValueError("dsam_fwd_nhwc_f32io: at least one output")
-    B, h, w, Ci = x_nhwc.shape
-    Co = bias4.shape[-1]
-    ho, wo = (h + 1) // 2, (w + 1) // 2
-    if tuple(code.shape) != (B, h, w):
-        raise ValueError(f"region code {tuple(code.shape)} does not match features {(B, h, w)}")
-    if residual_f32_nhwc is not None and (tuple(residual_f32_nhwc.shape) != (B, ho, wo, Co)
+    exp = (x_nhwc.shape[0], (x_nhwc.shape[1] + 1) // 2, (x_nhwc.shape[2] + 1) // 2, bias4.shape[-1])
+    if residual_f32_nhwc is not None and (tuple(residual_f32_nhwc.shape) != exp
                                           or residual_f32_nhwc.dtype != torch.float32):
-        raise ValueError(f"residual {tuple(residual_f32_nhwc.shape)} {residual_f32_nhwc.dtype} != float32 "
-                         f"{(B, ho, wo, Co)}")
-    out = torch.empty((B, ho, wo, Co), dtype=torch.bfloat16, device=x_nhwc.device) if want_bf16 else None
-    out32 = torch.empty((B, ho, wo, Co), dtype=torch.float32, device=x_nhwc.device) if want_f32 else None
-    b4 = bias4.detach().float().contiguous()
-    L = _lib.lib()
-    if plan is not None:
-        ws = _workspace(x_nhwc.device, L.rgbd_dsam_run_workspace_size(LEG_FWD, B, Ci, h, w, Co), "dsam_conv")
-        check(L.rgbd_dsam_fwd_nhwc_f32io_planned(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd),
-                                                 _p(b4), None, _p(out), _p(plan), _p(ws), _stream(x_nhwc.device),
-                                                 _p(residual_f32_nhwc), _p(out32)), "rgbd_dsam_fwd_nhwc_f32io_planned")
-        return out, out32
-    ws = _workspace(x_nhwc.device, L.rgbd_dsam_conv_workspace_size(RGBD_BF16, B, Ci, h, w, Co), "dsam_conv")
-    check(L.rgbd_dsam_fwd_nhwc_f32io(RGBD_BF16, _p(x_nhwc), _p(code), _p(info), B, Ci, h, w, Co, _p(wfwd), _p(b4),
-                                     None, _p(out), _p(ws), _stream(x_nhwc.device), _p(residual_f32_nhwc),
-                                     _p(out32)), "rgbd_dsam_fwd_nhwc_f32io")
-    return out, out32
+        raise ValueError(f"residual {tuple(residual_f32_nhwc.shape)} {residual_f32_nhwc.dtype} != float32 {exp}")
+    return _dsam_fwd_nhwc(x_nhwc, code, info, wfwd, bias4, None, residual_f32_nhwc, want_bf16, want_f32, plan)
 
 
 def dsam_bwd_data(gout_nhwc, code, wbwd, gin_nchw, want_nhwc=False, cin=None, gin_nhwc=None, want_nchw=True,
@@ -697,17 +689,11 @@ def dsam_bwd_data(gout_nhwc, code, wbwd, gin_nchw, want_nhwc=False, cin=None, gi
         raise ValueError("dsam_bwd_data: nothing to write")
     dx = torch.empty((B, Ci, h, w), dtype=gout_nhwc.dtype, device=gout_nhwc.device) if want_nchw else None
     dx_nhwc = torch.empty((B, h, w, Ci), dtype=gout_nhwc.dtype, device=gout_nhwc.device) if want_nhwc else None
-    L = _lib.lib()
     dt = _dtype_code(gout_nhwc)
-    if plan is not None:
-        ws = _workspace(gout_nhwc.device, L.rgbd_dsam_run_workspace_size(LEG_DX, B, Ci, h, w, Co), "dsam_conv")
-        check(L.rgbd_dsam_bwd_data_planned(dt, _p(gout_nhwc), _p(code), B, Ci, h, w, Co, _p(wbwd), _p(gin_nchw),
-                                           _p(gin_nhwc), _p(dx), _p(dx_nhwc), _p(plan), _p(ws),
-                                           _stream(gout_nhwc.device)), "rgbd_dsam_bwd_data_planned")
-        return dx, dx_nhwc
-    ws = _workspace(gout_nhwc.device, L.rgbd_dsam_conv_workspace_size(dt, B, Ci, h, w, Co), "dsam_conv")
-    check(L.rgbd_dsam_bwd_data(dt, _p(gout_nhwc), _p(code), B, Ci, h, w, Co, _p(wbwd), _p(gin_nchw), _p(gin_nhwc),
-                               _p(dx), _p(dx_nhwc), _p(ws), _stream(gout_nhwc.device)), "rgbd_dsam_bwd_data")
+    plan, ws = _dsam_leg(LEG_DX, code, Ci, Co, dt, plan, "dsam_conv")
+    check(_lib.lib().rgbd_dsam_bwd_data(dt, _p(gout_nhwc), _p(code), B, Ci, h, w, Co, _p(wbwd), _p(gin_nchw),
+                                        _p(gin_nhwc), _p(dx), _p(dx_nhwc), _p(plan), _p(ws),
+                                        _stream(gout_nhwc.device)), "rgbd_dsam_bwd_data")
     return dx, dx_nhwc
 
 
@@ -727,6 +713,8 @@ def dsam_bwd_weight(gout_nchw, x_nhwc, code, info, gout_nhwc=None, plan=None):
     _, h, w, Ci = x_nhwc.shape
     dev = ref.device
     dt = _dtype_code(ref)
+    if plan is not None and dt != RGBD_BF16:
+        raise ValueError("dsam_bwd_weight: a plan goes with the bfloat16 path")
     if dt == RGBD_BF16 and gout_nhwc is None:
         gout_nhwc = nchw_to_nhwc(gout_nchw)
     if gout_nhwc is not None and tuple(gout_nhwc.shape) != (B, ho, wo, Co):
@@ -734,18 +722,10 @@ def dsam_bwd_weight(gout_nchw, x_nhwc, code, info, gout_nhwc=None, plan=None):
     dconv = torch.empty((4, Co, Ci, 3, 3), dtype=torch.float32, device=dev)
     dproj = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=dev)
     dbias = torch.empty((4, Co), dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    if plan is not None:
-        if dt != RGBD_BF16:
-            raise ValueError("dsam_bwd_weight: a plan goes with the bfloat16 path")
-        ws = _workspace(dev, L.rgbd_dsam_run_workspace_size(LEG_DW, B, Ci, h, w, Co), "dsam_wgrad")
-        check(L.rgbd_dsam_bwd_weight_planned(dt, _p(gout_nchw), _p(gout_nhwc), _p(x_nhwc), _p(code), _p(info), B, Ci,
-                                             h, w, Co, _p(dconv), _p(dproj), _p(dbias), _p(plan), _p(ws),
-                                             _stream(dev)), "rgbd_dsam_bwd_weight_planned")
-        return dconv, dproj, dbias
-    ws = _workspace(dev, L.rgbd_dsam_bwd_weight_workspace_size(dt, B, Ci, h, w, Co), "dsam_wgrad")
-    check(L.rgbd_dsam_bwd_weight(dt, _p(gout_nchw), _p(gout_nhwc), _p(x_nhwc), _p(code), _p(info), B, Ci, h, w,
-                                 Co, _p(dconv), _p(dproj), _p(dbias), _p(ws), _stream(dev)), "rgbd_dsam_bwd_weight")
+    plan, ws = _dsam_leg(LEG_DW, code, Ci, Co, dt, plan, "dsam_wgrad")
+    check(_lib.lib().rgbd_dsam_bwd_weight(dt, _p(gout_nchw), _p(gout_nhwc), _p(x_nhwc), _p(code), _p(info), B, Ci,
+                                          h, w, Co, _p(dconv), _p(dproj), _p(dbias), _p(plan), _p(ws),
+                                          _stream(dev)), "rgbd_dsam_bwd_weight")
     return dconv, dproj, dbias
 
 
@@ -758,7 +738,7 @@ class _DwRun(ctypes.Structure):  # rgbd_dsam_dw_run
 
 def dsam_bwd_weight_multi(runs, info):
     """dW/db of bfloat16 DSAM legs that are ready together, their GEMMs in one persistent launch
-    (rgbd_dsam_bwd_weight_planned_multi).  ``runs``: up to two (gout_nhwc [B,ho,wo,Co], x_nhwc
+    (rgbd_dsam_bwd_weight_multi).  ``runs``: up to two (gout_nhwc [B,ho,wo,Co], x_nhwc
     [B,h,w,Ci], code [B,h,w], plan) tuples, each plan from dsam_plan(LEG_DW); returns per run
     (dconv, dproj, dbias), bitwise those of dsam_bwd_weight(None, ..., gout_nhwc=, plan=)."""
     if not 1 <= len(runs) <= 2:
@@ -778,12 +758,12 @@ def dsam_bwd_weight_multi(runs, info):
         dconv = torch.empty((4, Co, Ci, 3, 3), dtype=torch.float32, device=dev)
         dproj = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=dev)
         dbias = torch.empty((4, Co), dtype=torch.float32, device=dev)
-        ws = _workspace(dev, L.rgbd_dsam_run_workspace_size(LEG_DW, B, Ci, h, w, Co), f"dsam_wgrad_run{j}")
+        ws = _workspace(dev, L.rgbd_dsam_run_workspace_size(RGBD_BF16, LEG_DW, B, Ci, h, w, Co), f"dsam_wgrad_run{j}")
         arr[j] = _DwRun(gout_nhwc.data_ptr(), x_nhwc.data_ptr(), code.data_ptr(), B, Ci, h, w, Co, dconv.data_ptr(),
                         dproj.data_ptr(), dbias.data_ptr(), plan.data_ptr(), ws.data_ptr())
         outs.append((dconv, dproj, dbias))
-    check(L.rgbd_dsam_bwd_weight_planned_multi(len(runs), arr, _p(info), _stream(runs[0][0].device)),
-          "rgbd_dsam_bwd_weight_planned_multi")
+    check(L.rgbd_dsam_bwd_weight_multi(len(runs), arr, _p(info), _stream(runs[0][0].device)),
+          "rgbd_dsam_bwd_weight_multi")
     return outs
 
 

@@ -109,8 +109,8 @@ def _sample(maps, coords):
     out = torch.empty((N, P), dtype=torch.float32, device=maps.device)
     if N:
         code = RGBD_BF16 if maps.dtype == torch.bfloat16 else RGBD_F32
-        check(_lib.lib().rgbd_point_sample_t(code, _p(maps), N, h, w, _p(coords), N // G, P, _p(out),
-                                             _stream(maps.device)), "rgbd_point_sample_t")
+        check(_lib.lib().rgbd_point_sample(code, _p(maps), N, h, w, _p(coords), N // G, P, _p(out),
+                                           _stream(maps.device)), "rgbd_point_sample")
     return out
 
 

@@ -90,9 +90,9 @@ def ratio_predictor_forward(module, depth_image: torch.Tensor) -> torch.Tensor:
         module._rgbd_dropout_seed = (torch.initial_seed() * 1000003 + next(_seed_counter) * 0x10000) & 0xFFFFFFFFFFFF
     # test hook: "phase2" computes the bf16 train-mode gated features by the phase-2 recompute
     flags = 1 if getattr(module, "train_route", "gate") == "phase2" else 0  # RGBD_RATIO_F_PHASE2
-    check(L.rgbd_ratio_forward_ex(code, int(training), ctypes.c_float(momentum), ctypes.c_void_p(d.data_ptr()),
-                                  d.stride(0), B, H, W, _p(blob), bn_arr, ctypes.c_ulonglong(module._rgbd_dropout_seed),
-                                  _p(ctr), _p(ratio), _p(ws), flags, _stream(d.device)), "rgbd_ratio_forward_ex")
+    check(L.rgbd_ratio_forward(code, int(training), ctypes.c_float(momentum), ctypes.c_void_p(d.data_ptr()),
+                               d.stride(0), B, H, W, _p(blob), bn_arr, ctypes.c_ulonglong(module._rgbd_dropout_seed),
+                               _p(ctr), _p(ratio), _p(ws), flags, _stream(d.device)), "rgbd_ratio_forward")
     if training:  # one multi-tensor launch for the six BatchNorm counters (torch's BatchNorm2d
         # increments them before normalising; with a set momentum nothing reads them, so they follow
         # the kernels: queued ahead of them the launch delayed the predictor's first kernel)

@@ -57,7 +57,10 @@ class CapturedTrainStep:
                 clear()
         torch.cuda.current_stream().wait_stream(self.stream)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(self.graph, stream=self.stream):
+        # thread_local: under the default global mode every thread's event query fails while this
+        # capture is open, and ProcessGroupNCCL's watchdog polls the warm-up's collectives from a
+        # thread of its own (hipErrorStreamCaptureUnsupported there ends the process)
+        with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
             self.outs = self.fb()
             if opt is not None:
                 self.opt.step()

@@ -27,12 +27,34 @@ def test_argument_validation_without_device():
     null = ctypes.c_void_p(0)
     # null pointers / bad sizes are rejected on the host with RGBD_E_ARG, nothing launched
     assert L.rgbd_assemble_pixel_values(null, null, 1, 4, 4, null, null, null) == -1
-    assert L.rgbd_dsam_fwd(0, null, null, null, 1, 32, 8, 8, 64, null, null, null, null, null, null, null) == -1
+    assert L.rgbd_dsam_fwd(0, null, null, null, 1, 32, 8, 8, 64, null, null, null, null, null, null, null, null) == -1
     fake = ctypes.c_void_p(0x1000)
     # Cin not a multiple of 8 -> unsupported shape
-    assert L.rgbd_dsam_fwd(0, fake, fake, fake, 1, 12, 8, 8, 64, fake, fake, null, fake, null, null, null) == -2
+    assert L.rgbd_dsam_fwd(0, fake, fake, fake, 1, 12, 8, 8, 64, fake, fake, null, fake, null, null, null, null) == -2
     # unknown dtype
     assert L.rgbd_nchw_to_nhwc(7, fake, fake, 1, 1, 1, 1, null) == -3
+
+
+def test_dsam_run_calls_argument_validation_without_device():
+    """The other K5 run calls, refused on the host like rgbd_dsam_fwd: null pointers RGBD_E_ARG and
+    a contraction channel count that is no multiple of 8 RGBD_E_SHAPE with RGBD_F32 (dX contracts
+    over Cout, so its check is Cout % 8; dW's is Cin % 8 as the forward's); with RGBD_BF16 every run
+    call needs its leg's plan (NULL: RGBD_E_ARG)."""
+    L = _lib.lib()
+    null, fake = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
+    f32, bf = _lib.RGBD_F32, _lib.RGBD_BF16
+    assert L.rgbd_dsam_bwd_data(f32, null, null, 1, 32, 8, 8, 64, null, null, null, null, null, null, null, null) == -1
+    assert L.rgbd_dsam_bwd_data(f32, fake, fake, 1, 32, 8, 8, 12, fake, null, null, fake, null, null, fake, null) == -2
+    assert L.rgbd_dsam_bwd_weight(f32, null, null, null, null, null, 1, 32, 8, 8, 64, null, null, null, null, null,
+                                  null) == -1
+    assert L.rgbd_dsam_bwd_weight(f32, fake, null, fake, fake, fake, 1, 12, 8, 8, 64, fake, fake, fake, null, fake,
+                                  null) == -2
+    assert L.rgbd_dsam_fwd(bf, fake, fake, fake, 1, 32, 8, 8, 64, fake, fake, null, fake, null, null, fake, null) == -1
+    assert L.rgbd_dsam_fwd_nhwc(bf, fake, fake, fake, 1, 32, 8, 8, 64, fake, fake, null, fake, null, null, null, fake,
+                                null) == -1
+    assert L.rgbd_dsam_bwd_data(bf, fake, fake, 1, 32, 8, 8, 64, fake, null, null, fake, null, null, fake, null) == -1
+    assert L.rgbd_dsam_bwd_weight(bf, null, fake, fake, fake, fake, 1, 32, 8, 8, 64, fake, fake, fake, null, fake,
+                                  null) == -1
 
 
 def test_ops_refuse_cpu_tensors():

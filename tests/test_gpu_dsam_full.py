@@ -212,7 +212,7 @@ def test_dsam_fwd_nhwc_equals_nchw_path(k):
 
 @pytest.mark.parametrize("shape", [(2, 96, 120, 160), (3, 192, 13, 17), (2, 384, 7, 9)])
 def test_dggm_cp1_nhwc_equals_nchw(shape):
-    """rgbd_dggm_fuse_fwd_multi_mixed with cp1 in NHWC gives bitwise the NCHW-cp1 result."""
+    """rgbd_dggm_fuse_fwd_multi with cp1 in NHWC gives bitwise the NCHW-cp1 result."""
     import golden_inputs as gi
     B, C, h, w = shape
     H, W = 4 * h, 4 * w

@@ -1,9 +1,10 @@
 """Planning ahead (include/rgbd_hip.h rgbd_dsam_plan): every bf16 DSAM leg run with a plan made
 earlier — all forward / dX legs of the three DSAMs planned by one call, the dW legs by another —
-gives bitwise the outputs of the plain entry points, which plan inside the call.  Shapes: the
-bench's 640x480 B=8 pyramid and a ragged one (97x131 input, odd feature sizes), region codes
-from the HIP decomposition.  Reference path: custom_model.py:682-699 (DSAModule.forward); the
-parity of the plain entry points themselves is test_gpu_dsam_full.py / test_gpu_parity.py."""
+gives bitwise the outputs of the same leg run with a plan made by the wrapper for that leg
+alone.  Shapes: the bench's 640x480 B=8 pyramid and a ragged one (97x131 input, odd feature
+sizes), region codes from the HIP decomposition.  Reference path: custom_model.py:682-699
+(DSAModule.forward); the parity of the legs themselves is test_gpu_dsam_full.py /
+test_gpu_parity.py."""
 import pytest
 import torch
 
@@ -87,9 +88,9 @@ def test_decompose_code_masks(H, W, B):
 
 @pytest.mark.parametrize("H,W,B,pairs", [(480, 640, 8, [(1, 0), (2, 1), (0,)]), (97, 131, 3, [(1, 0), (2, 0)])])
 def test_joint_dw_bitwise(H, W, B, pairs):
-    """rgbd_dsam_bwd_weight_planned_multi: the dW GEMMs of two legs in one persistent launch give
-    per leg bitwise the gradients of the one-leg planned entry point (the hot path runs dsam1 and
-    dsam0 this way; hot_path.JOINT_DW)."""
+    """rgbd_dsam_bwd_weight_multi: the dW GEMMs of two legs in one persistent launch give per leg
+    bitwise the gradients of the one-leg entry point (the hot path runs dsam1 and dsam0 this way;
+    hot_path.JOINT_DW)."""
     planes, _, _ = synthetic.make_batch(11, B, H, W)
     d3 = torch.from_numpy(planes[:, 3:6]).to(DEV)
     sizes = _sizes(H, W)

@@ -290,6 +290,36 @@ def test_nchw_to_nhwc_family(shape):
     assert torch.equal(ops.nchw_to_nhwc_multi([xb])[0], xb.permute(0, 2, 3, 1).contiguous())
 
 
+def test_dsam_legs_with_wrapper_made_plans():
+    """bf16 DSAM legs called without ``plan=``: the wrapper plans the leg alone (ops.dsam_plan) and
+    sizes the workspace for the run part only (rgbd_dsam_run_workspace_size).  97x131, B = 3
+    (pyramid 25x33, 13x17, 7x9): the linear 128-pixel tiles and the 8x16 tiles are both ragged and
+    a tile spans several chunks, the smallest shapes at which the partial-tile carve can go wrong.
+    Plans, partial tiles, channel sums and outputs all sit between guards."""
+    from rgbd_amd import ops, synthetic
+    B, H, W = 3, 97, 131
+    planes, _, _ = synthetic.make_batch(7, B, H, W)
+    d3 = torch.from_numpy(planes[:, 3:6]).to(DEV)
+    sizes = [(25, 33), (13, 17), (7, 9)]
+    codes, info = ops.edsam_decompose(d3, torch.linspace(0.05, 0.45, B, device=DEV), sizes)
+    g = torch.Generator().manual_seed(5)
+    packs = []
+    for ci, co in [(96, 192), (192, 384)]:
+        cw, pw = _randn(g, (4, co, ci, 3, 3), scale=0.03), _randn(g, (co, ci, 3, 3), scale=0.03)
+        packs.append(ops.dsam_pack(cw, pw, BF16))
+    b4 = _randn(g, (4, 192), scale=0.1)
+    x0 = _randn(g, (B, 25, 33, 96), BF16)
+    res0, gy0 = _randn(g, (B, 13, 17, 192), BF16), _randn(g, (B, 13, 17, 192), BF16, 0.1)
+    gy1, gin1 = _randn(g, (B, 7, 9, 384), BF16, 0.1), _randn(g, (B, 13, 17, 192), BF16)
+    _sweep(lambda x, c, i, wf, b, r: ops.dsam_fwd_nhwc(x, c, i, wf, b, residual_nhwc=r),
+           x0, codes[0], info, packs[0][0], b4, res0)
+    _sweep(lambda gy, c, wb, gin: ops.dsam_bwd_data(gy, c, wb, None, want_nhwc=True, want_nchw=False, gin_nhwc=gin)[1],
+           gy1, codes[1], packs[1][1], gin1)
+    _sweep(lambda gy, x, c, i: ops.dsam_bwd_weight(None, x, c, i, gout_nhwc=gy), gy0, x0, codes[0], info)
+    _sweep(lambda x, c, i, wf, b, r: ops.dsam_fwd(x, c, i, wf, b, residual=r, want_nhwc=True),
+           x0, codes[0], info, packs[0][0], b4, res0.permute(0, 3, 1, 2).contiguous())
+
+
 # ------------------------------------------------------------------ 3. whole model
 _MODEL = []
 

@@ -108,7 +108,7 @@ def dsam_setup():
 @pytest.mark.parametrize("k", [0, 1, 2])
 @pytest.mark.parametrize("H,W,B", [(97, 131, 3), (240, 320, 2)])
 def test_dsam_f32io_epilogue_bitwise(dsam_setup, H, W, B, k, planned):
-    """rgbd_dsam_fwd_nhwc_f32io[_planned] on the three real DSAMs: 97x131, B = 3 (ragged tiles,
+    """rgbd_dsam_fwd_nhwc's float32 interface on the three real DSAMs: 97x131, B = 3 (ragged tiles,
     several split-K chunks) and 240x320, B = 2."""
     sizes, codes, info, per = dsam_setup(H, W, B)
     (h, w), (ci, co) = sizes[k], DSAM_CH[k]
@@ -150,7 +150,7 @@ def test_dsam_f32io_epilogue_bitwise(dsam_setup, H, W, B, k, planned):
 # ------------------------------------------------------------------ 3. DGGM, float32 NHWC cp1
 @pytest.mark.parametrize("shape", [(2, 96, 120, 160), (3, 192, 13, 17), (2, 384, 7, 9)])
 def test_dggm_f32_cp1_nhwc_equals_nchw(shape):
-    """rgbd_dggm_fuse_fwd_multi_mixed (RGBD_F32) with cp1 in NHWC gives bitwise the NCHW-cp1
+    """rgbd_dggm_fuse_fwd_multi (RGBD_F32) with cp1 in NHWC gives bitwise the NCHW-cp1
     result: the path the mode's outputs take (shapes of test_dggm_cp1_nhwc_equals_nchw)."""
     B, C, h, w = shape
     pv = torch.from_numpy(gi.pixel_values(13, B, 4 * h, 4 * w)).to(DEV)

@@ -49,7 +49,7 @@ def _case(seed, B=3, Q=100, L=49, H=60, W=80, counts=(5, 0, 23)):
 
 
 def test_point_sample_bf16_maps_equal_widened_float32():
-    """rgbd_point_sample_t on bf16 maps (the logits under autocast, no float32 copy) gives the
+    """rgbd_point_sample on bf16 maps (the logits under autocast, no float32 copy) gives the
     bits of the float32 kernel on the same maps widened."""
     g = torch.Generator(device=DEV).manual_seed(3)
     maps = torch.randn((12, 120, 160), generator=g, device=DEV).to(torch.bfloat16)

@@ -10,7 +10,7 @@ import torch
 from rgbd_amd import _lib, ops
 from rgbd_amd.hot_path import float32_interface, hot_path, prepare
 
-NEW = ("rgbd_nchw_to_nhwc_multi_f32", "rgbd_dsam_fwd_nhwc_f32io", "rgbd_dsam_fwd_nhwc_f32io_planned")
+NEW = ("rgbd_nchw_to_nhwc_multi_f32", "rgbd_dsam_fwd_nhwc")
 E_ARG, E_SHAPE, E_DTYPE = -1, -2, -3
 
 
@@ -52,21 +52,17 @@ def test_layout_entry_point_argument_checks():
     assert f(1, _job(fake, fake, 1, 8, 2, 2, 7), null) == E_DTYPE
 
 
-@pytest.mark.parametrize("planned", [False, True])
-def test_dsam_f32io_entry_point_argument_checks(planned):
-    """The checks of rgbd_dsam_fwd_nhwc[_planned] before any launch, plus the new pointers':
-    a compute dtype other than RGBD_BF16 is RGBD_E_DTYPE; null pointers, bad sizes, no output at
-    all, a bf16 residual beside a float32 pointer and misaligned float32 pointers RGBD_E_ARG."""
+def test_dsam_f32io_entry_point_argument_checks():
+    """The checks of rgbd_dsam_fwd_nhwc before any launch, its float32 pointers' included: a compute
+    dtype other than RGBD_BF16 is RGBD_E_DTYPE; null pointers, bad sizes, no output at all, a bf16
+    residual beside a float32 pointer, misaligned float32 pointers and no plan RGBD_E_ARG."""
     L = _lib.lib()
     null = ctypes.c_void_p(0)
     fake = ctypes.c_void_p(4096)
 
     def call(dt, x, out, ws, res16=null, res32=null, out32=null, B=1, plan=fake):
-        if planned:
-            return L.rgbd_dsam_fwd_nhwc_f32io_planned(dt, x, fake, fake, B, 32, 8, 8, 64, fake, fake, res16, out, plan,
-                                                      ws, null, res32, out32)
-        return L.rgbd_dsam_fwd_nhwc_f32io(dt, x, fake, fake, B, 32, 8, 8, 64, fake, fake, res16, out, ws, null, res32,
-                                          out32)
+        return L.rgbd_dsam_fwd_nhwc(dt, x, fake, fake, B, 32, 8, 8, 64, fake, fake, res16, out, res32, out32, plan, ws,
+                                    null)
     bf, f32 = _lib.RGBD_BF16, _lib.RGBD_F32
     assert call(f32, fake, fake, fake, out32=fake) == E_DTYPE
     assert call(7, fake, fake, fake, out32=fake) == E_DTYPE
@@ -78,8 +74,7 @@ def test_dsam_f32io_entry_point_argument_checks(planned):
     assert call(bf, fake, fake, fake, res16=fake, res32=fake) == E_ARG
     assert call(bf, fake, fake, fake, out32=ctypes.c_void_p(4100)) == E_ARG
     assert call(bf, fake, fake, fake, res32=ctypes.c_void_p(4104), out32=fake) == E_ARG
-    if planned:
-        assert call(bf, fake, fake, fake, out32=fake, plan=null) == E_ARG
+    assert call(bf, fake, fake, fake, out32=fake, plan=null) == E_ARG
 
 
 def _cpu_inputs():
