@@ -328,6 +328,37 @@ int rgbd_adamw_multi_shadow(int n, float* const* params, const float* const* gra
                             const float* step, double lr, double beta1, double beta2, double eps,
                             double weight_decay, void* stream);
 
+/* ---------------------------------------------------------------- gradient-norm clipping
+ * The Trainer's max_grad_norm (TrainingArguments' default 1.0; config.json does not set it):
+ * torch.nn.utils.clip_grad_norm_ as called from Trainer._clip_grad_norm, behind finetuning.py:98,
+ * L2 norm over all gradients, error_if_nonfinite=False.  No atomics anywhere: the norm is bitwise
+ * reproducible run to run and independent of workgroup scheduling and of pointer alignment.
+ *
+ * rgbd_grad_sumsq_multi (replaces clip_grad_norm_'s _foreach_norm + stack): the sums of squares of
+ *   n <= 128 fp32 tensors (grads, numel: host arrays), one double per 4096-element chunk, written
+ *   to ws[slot0 + c] for this call's c-th chunk (tensor order, then chunk order).  Squares and sums
+ *   are double from the element on.  rgbd_grad_sumsq_workspace_size(n, numel): the bytes these n
+ *   tensors' partials take (8 per chunk; pure, numel is a host array), so a parameter list longer
+ *   than one table fills one array with several calls, slot0 advancing by size / 8. */
+size_t rgbd_grad_sumsq_workspace_size(int n, const long long* numel);
+int rgbd_grad_sumsq_multi(int n, const float* const* grads, const long long* numel, void* ws, long long slot0,
+                          void* stream);
+/* rgbd_grad_norm_finalize (replaces clip_grad_norm_'s vector_norm of the norms and its
+ *   clip_coef / clamp): sums ws[0 .. n_partials) in double in a fixed order and writes
+ *   out[0] = total_norm, out[1] = min(1, max_norm / (total_norm + 1e-6)) (device, float32; the
+ *   coefficient in float32 by torch's expression: a NaN norm gives NaN, an infinite one 0). */
+int rgbd_grad_norm_finalize(const void* ws, long long n_partials, double max_norm, float* out, void* stream);
+/* rgbd_adamw_multi_scaled (replaces clip_grad_norm_'s _foreach_mul_ + the optimizer step): the
+ *   update of rgbd_adamw_multi on g * *grad_scale (device float32, e.g. out + 1 above); grads are
+ *   not written.  shadows as in rgbd_adamw_multi_shadow, or NULL for no bfloat16 copies. */
+int rgbd_adamw_multi_scaled(int n, float* const* params, const float* const* grads, float* const* exp_avg,
+                            float* const* exp_avg_sq, void* const* shadows, const long long* numel,
+                            const float* step, const float* grad_scale, double lr, double beta1, double beta2,
+                            double eps, double weight_decay, void* stream);
+/* rgbd_scale_multi (replaces clip_grad_norm_'s _foreach_mul_ where the clipped gradients must be
+ *   left in p.grad): x *= *scale in place over n <= 128 fp32 tensors; scale on the device. */
+int rgbd_scale_multi(int n, float* const* tensors, const long long* numel, const float* scale, void* stream);
+
 /* ---------------------------------------------------------------- K4 ratio predictor
  * EnhancedDepthImageRatioPredictor.forward (custom_model.py:1444-1487) for the batch:
  * depth3 (float32 planes as for the decomposition) -> ratio float32 [B] in [0.01, 0.5],

@@ -64,6 +64,12 @@ SIGNATURES = {
                              ctypes.c_double, ctypes.c_double, _P]),
     "rgbd_adamw_multi_shadow": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
+    "rgbd_grad_sumsq_workspace_size": (_SZ, [_I, _P]),
+    "rgbd_grad_sumsq_multi": (_I, [_I, _P, _P, _P, _LL, _P]),
+    "rgbd_grad_norm_finalize": (_I, [_P, _LL, ctypes.c_double, _P, _P]),
+    "rgbd_adamw_multi_scaled": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
+    "rgbd_scale_multi": (_I, [_I, _P, _P, _P, _P]),
     "rgbd_dsam_packed_elems": (_LL, [_I, _I, _I]),
     "rgbd_dsam_pack_weights": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "rgbd_dsam_code_masks": (_I, [_I, _P, _P, _P, _P]),

@@ -183,7 +183,8 @@ class InBackwardOptimizer:
     launch at the end (small groups alone make latency-bound optimizer launches).  AdamW updates
     every parameter from its own gradient and state only, so parameters and optimizer state are
     bitwise those of one ``optimizer.step()`` after the backward (this step has no gradient
-    clipping; a global-norm clip would need every gradient first).  With a reducer (data
+    clipping; a global-norm clip needs every gradient first, so an optimizer built with
+    ``max_grad_norm`` is refused: step it after the backward).  With a reducer (data
     parallel) a part's step first waits, on its stream, for its groups' all-reduces and uses the
     means: DDP + step.  After the backward ``p.grad`` holds this rank's local gradients
     (autograd's assignment, no kernel); clear them with ``zero_grad(set_to_none=True)``."""
@@ -194,6 +195,11 @@ class InBackwardOptimizer:
         if sorted(i for s in self.steps for i in s) != list(range(len(self.groups))):
             raise ValueError(f"steps {steps} must partition groups 0..{len(self.groups) - 1}")
         self.opts = [make_opt([p for i in s for p in self.groups[i]]) for s in self.steps]
+        if any(getattr(o, "max_grad_norm", None) is not None for o in self.opts):
+            raise ValueError("InBackwardOptimizer steps each part before the other parts have gradients, so an "
+                             "optimizer built with max_grad_norm would clip by a partial norm, not the global one; "
+                             "to clip, step after the backward instead (one HipAdamW(max_grad_norm=...).step(), "
+                             "after OverlappedGradReducer.finish() under data parallelism)")
         self.reducer = reducer
         self.held = {}
 

@@ -6,7 +6,11 @@ instances), random-init weights.  Two arms on the same weights and inputs:
   hf    — hot path (bf16 MFMA), the f1/f2/f3 modules as the installed Hugging Face code
   hip_det — the hip arm in deterministic mode (rgbd_amd.determinism: atomic-free MSDA and
           point-sample backward, 1-d class loss); "--arms hip,hip_det" times both modes in one process
-with the HF parts in float32 or under torch.autocast(bfloat16) (--amp).  Prints one JSON line."""
+with the HF parts in float32 or under torch.autocast(bfloat16) (--amp).  Prints one JSON line.
+--clip X: the arms step with HipAdamW(**HF_TRAINER_ADAMW, max_grad_norm=X), the Trainer's AdamW
+with its global-norm clip on the device, and report the last step's gradient
+norm; an arm named "<arm>:noclip" keeps the default optimizer (torch's fused AdamW, no clip), so
+"--arms hip:noclip,hip --clip 1.0" times both in one process."""
 import argparse
 import json
 import sys
@@ -28,6 +32,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--amp", type=int, default=1)
     ap.add_argument("--arms", default="hip,hf")
+    ap.add_argument("--clip", type=float, default=None, metavar="X",
+                    help="max_grad_norm of a HipAdamW step (default: no clip, torch's fused AdamW)")
     args = ap.parse_args()
     from rgbd_amd import (deform_attn, dense, determinism, init as winit, mask_predictor, masked_attention, point_loss,
                           ops, swin, synthetic)
@@ -40,8 +46,12 @@ def main():
     rgb = torch.from_numpy(np.stack([s["rgb_u8"] for s in scenes])).contiguous().to(dev)
     mask_labels = [torch.from_numpy(s["masks"].astype(np.float32)).to(dev) for s in scenes]
     class_labels = [torch.from_numpy(s["classes"]).to(dev) for s in scenes]
-    res = {"batch": B, "shape": f"{W}x{H}", "amp_bf16": bool(args.amp)}
-    for ai, arm in enumerate(args.arms.split(",")):
+    res = {"batch": B, "shape": f"{W}x{H}", "amp_bf16": bool(args.amp), "clip": args.clip}
+    for ai, name in enumerate(args.arms.split(",")):
+        arm, _, flag = name.partition(":")
+        if flag not in ("", "noclip"):
+            raise SystemExit(f"unknown arm suffix in {name!r}")
+        clip = None if flag == "noclip" else args.clip
         torch.manual_seed(0)
         m = CustomMask2FormerForUniversalSegmentation(standard_config(48), version="0.4.0")
         winit.init_deterministic(m)
@@ -63,7 +73,12 @@ def main():
         mode_before = determinism.get_state()
         if arm == "hip_det":
             determinism.set_deterministic(True)
-        opt = torch.optim.AdamW([p for p in m.parameters() if p.requires_grad], lr=1e-5, fused=True)
+        params = [p for p in m.parameters() if p.requires_grad]
+        if clip is None:
+            opt = torch.optim.AdamW(params, lr=1e-5, fused=True)
+        else:
+            from rgbd_amd.optim import HF_TRAINER_ADAMW, HipAdamW
+            opt = HipAdamW(params, **HF_TRAINER_ADAMW, max_grad_norm=clip)
 
         def step():
             pv = ops.assemble_pixel_values(depth, rgb)
@@ -81,9 +96,10 @@ def main():
             loss = step()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
-        key = arm if arm not in res else f"{arm}_{ai}"
+        key = name if name not in res else f"{name}_{ai}"
         res[key] = {"img_s": round(B / dt, 2), "ms_per_step": round(dt * 1e3, 1), "loss": round(float(loss.detach()), 4),
-                    "deterministic": determinism.is_deterministic()}
+                    "deterministic": determinism.is_deterministic(), "clip": clip,
+                    "grad_norm": None if clip is None else round(float(opt.grad_norm), 4)}
         del m, opt
         determinism.set_deterministic(mode_before)
         torch.cuda.empty_cache()
