@@ -238,14 +238,16 @@ def _hot_modules(dtype):
     return dsams, dg.to(DEV)
 
 
+@pytest.mark.parametrize("H,W,B", [(240, 320, 2), (90, 125, 2), (97, 131, 3)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_hot_path_fused_vs_oracle(dtype):
-    """The fused HotPathFunction at 240x320, B=2 with injected ratios: the 4 backbone
-    features and every hot-path parameter gradient against the oracle (custom_model.py:324-355)."""
+def test_hot_path_fused_vs_oracle(dtype, H, W, B):
+    """The fused HotPathFunction with injected ratios: the 4 backbone features and every hot-path
+    parameter gradient against the oracle (custom_model.py:324-355).  240x320 is the training
+    shape; 97x131 gives Swin maps 25x33, 13x17, 7x9, 4x5 (K2 at PX = 1 three times and PX = 4, odd
+    stride-2 DSAM cascades) and 90x125 adds K1's non-quad path in the same step."""
     from rgbd_amd.hot_path import hot_path
-    H, W, B = 240, 320, 2
     pv = torch.from_numpy(gi.pixel_values(7, B, H, W))
-    ratios = torch.tensor([[0.2], [0.07]], dtype=torch.float32)
+    ratios = torch.tensor([[0.2], [0.07], [0.33]][:B], dtype=torch.float32)
     sizes = gi.swin_sizes(H, W)
     colors = [torch.from_numpy(gi.feature(f"hp.c{k}", (B, c, *sizes[k])))
               for k, c in enumerate([96, 192, 384, 768])]
