@@ -474,6 +474,41 @@ int rgbd_point_losses(const float* logits, const float* labels, int N, int P, fl
 int rgbd_point_losses_bwd(const float* logits, const float* labels, int N, int P, const float* sums,
                           const float* g_ce, const float* g_dice, float* glogits, void* stream);
 
+/* ---------------------------------------------------------------- f3 classification loss
+ * The class term of the Mask2Former loss (transformers 5.15 modeling_mask2former.py
+ * Mask2FormerLoss.loss_labels :548-578): every (image, query) row's target built from the batched
+ * assignment, then nn.CrossEntropyLoss(weight) over the N = B Q rows.  No float atomics; every
+ * sum's order is a function of (B, Q, C1) alone, so the loss bits do not depend on scheduling.
+ * rgbd_class_loss_fwd: logits dtype [B][Q][C1] (RGBD_F32, or RGBD_BF16 widened exactly: no
+ *   float32 copy), w float32 [C1] (the last class is "no object").  The matches as the batched
+ *   assignment leaves them: rows_all / cols_all int64 [M] (query / target index within the image),
+ *   moff / toff int32 [B+1] (match / target offsets per image), labels_all int64 [T] (every
+ *   image's class labels, concatenated).  Row b Q + rows_all[m] gets the target
+ *   labels_all[toff[b] + cols_all[m]] for m in [moff[b], moff[b+1]); every other row C1 - 1.
+ *   M == 0 is legal (rows_all, cols_all, labels_all may then be NULL).  A match whose query,
+ *   target or class index is out of range is ignored (nothing is accessed out of bounds).
+ *   Outputs (device): *loss = sum_i w[t_i] (lse_i - x[i][t_i]) / sum_i w[t_i], all float32, the
+ *   row maximum subtracted before exp (a -inf logit contributes 0); the denominator is not
+ *   guarded (an all-zero weight sum gives NaN, as torch does).  Kept for the backward: *wsum =
+ *   sum_i w[t_i]; target int32 [N]; stats float32 [2][N] = (max_c x[i][c], log sum_c exp(x[i][c] -
+ *   max)) — lse_i is their sum, kept in two parts because at logits of 1e4 its float32 spacing
+ *   would be the relative error of every rebuilt probability.  ws: rgbd_class_loss_workspace_size
+ *   bytes.  Two launches (rows -> per-block pairs, one workgroup -> the loss), no memset or copy.
+ * rgbd_class_loss_bwd: glogits[i][c] = g w[t_i]/wsum (exp((x[i][c] - max_i) - logsum_i) - [c ==
+ *   t_i]) in the logits' dtype (bf16 rounds once, at the store); g, wsum read on the device.  One
+ *   launch.
+ * Both: a NULL pointer, or B, Q or C1 <= 0 (fwd: M or T < 0): RGBD_E_ARG; another dtype code:
+ *   RGBD_E_DTYPE; C1 < 2, C1 > rgbd_class_loss_max_classes() (512: 16 rows of float32 in LDS), or
+ *   B Q C1 >= 2^31: RGBD_E_SHAPE — all checked before any HIP call. */
+int rgbd_class_loss_max_classes(void);
+size_t rgbd_class_loss_workspace_size(int B, int Q, int C1);
+int rgbd_class_loss_fwd(int dtype, const void* logits, const float* w, int B, int Q, int C1,
+                        const long long* rows_all, const long long* cols_all, int M, const int* moff, const int* toff,
+                        const long long* labels_all, int T, void* ws, float* loss, float* wsum, float* stats,
+                        int* target, void* stream);
+int rgbd_class_loss_bwd(int dtype, const void* logits, const float* w, int B, int Q, int C1, const float* stats,
+                        const int* target, const float* wsum, const float* g, void* glogits, void* stream);
+
 /* The decoder memory of one feature level (Mask2FormerTransformerModule.forward :2095-2109):
  *   out[p][b][c] = proj[b][c][p] + embed[c]   (proj dtype [B][C][HW]: the input projection's
  *   output; embed float32 [C]: level_embed.weight[level]; out float32 [HW][B][C]: the permuted

@@ -93,6 +93,10 @@ SIGNATURES = {
                                    ctypes.c_float, _P, _P]),
     "rgbd_point_losses": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "rgbd_point_losses_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "rgbd_class_loss_max_classes": (_I, []),
+    "rgbd_class_loss_workspace_size": (_SZ, [_I, _I, _I]),
+    "rgbd_class_loss_fwd": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "rgbd_class_loss_bwd": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rgbd_msda_fwd": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rgbd_msda_bwd": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "rgbd_msda_bwd_emit": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

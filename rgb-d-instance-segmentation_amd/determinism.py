@@ -3,8 +3,10 @@
 With the mode on, the two value-gradient scatters that otherwise sum with float atomics — the
 MSDA backward (csrc/msda.hip) and the point-sample backward (csrc/point_loss.hip) — are computed
 by an emit pass, a stable sort and a per-destination sum in an order fixed by the inputs
-(csrc/ordered_gather.hpp), and the class loss takes ATen's atomic-free 1-d NLL kernel: two
-training steps from the same state, seeds and inputs then give the same bits.
+(csrc/ordered_gather.hpp), and the class loss, where it still runs on torch
+(point_loss.HIP_CLASS_LOSS off; csrc/class_loss.hip is atomic-free in any mode), takes ATen's
+atomic-free 1-d NLL kernel: two training steps from the same state, seeds and inputs then give
+the same bits.
 
 The state is tri-state.  ``None`` (the initial value) follows
 ``torch.are_deterministic_algorithms_enabled()``; ``RGBD_DETERMINISTIC=1`` / ``=0`` in the

@@ -10,6 +10,9 @@ them.  Here the sampling (``rgbd_point_sample`` / ``_bwd``), the cost reduction
 coordinates (``torch.rand``), the uncertainty ``torch.topk`` and the index gathers stay torch
 calls in the reference's order, so the RNG stream and the selected point set are the reference's
 (the set: the top-k is taken unsorted, the loss sums do not depend on the points' order).
+The class term, ``Mask2FormerLoss.loss_labels`` (:548-578), is ``class_loss``: the target build
+from the batched assignment and the weighted cross-entropy in ``rgbd_class_loss_fwd`` / ``_bwd``
+(csrc/class_loss.hip, no atomics).
 
 ``install(model)`` swaps the HF loss (and its matcher) for ``HipMask2FormerLoss`` /
 ``matcher.HipHungarianMatcher`` in place; ``uninstall`` restores them.
@@ -22,12 +25,18 @@ from transformers.models.mask2former.modeling_mask2former import Mask2FormerHung
 
 from . import _lib, determinism
 from ._lib import RGBD_BF16, RGBD_F32, check
-from .ops import LsaResult, _need_cuda, _p, _stream, device_const, device_vec, ordered_gather, ordered_sort
+from .ops import (LsaResult, _need_cuda, _p, _stream, _workspace, device_const, device_vec, ordered_gather,
+                  ordered_sort)
 
 # loss_masks' uncertainty top-k: unsorted by default (the loss terms are sums over the point set,
 # so only the float summation order changes; the segmented sort cost ~2.4 ms per whole-model
 # step); True — or RGBD_SORTED_TOPK=1 — takes the reference's sorted selection (parity runs)
 SORTED_TOPK = os.environ.get("RGBD_SORTED_TOPK", "0") == "1"
+
+# loss_labels' weighted cross-entropy on rgbd_class_loss_fwd / _bwd (three launches per decoder
+# output, deterministic in any mode); False — or RGBD_HIP_CLASS_LOSS=0 — restores the torch target
+# build + nn.CrossEntropyLoss path exactly (A/B runs)
+HIP_CLASS_LOSS = os.environ.get("RGBD_HIP_CLASS_LOSS", "1") != "0"
 
 
 # one entry each, shared by the loss and its matcher (the final and the nine auxiliary outputs of a
@@ -189,6 +198,86 @@ class _PointLosses(torch.autograd.Function):
         return gx, None
 
 
+def class_loss_max_classes() -> int:
+    """The largest class count (no-object included) rgbd_class_loss_fwd takes."""
+    return int(_lib.lib().rgbd_class_loss_max_classes())
+
+
+def _offsets(counts):
+    offs = [0]
+    for n in counts:
+        offs.append(offs[-1] + int(n))
+    return offs
+
+
+def class_loss_forward(logits, weight, rows_all, cols_all, moff, toff, labels):
+    """rgbd_class_loss_fwd on logits [B, Q, C1] (float32 or bfloat16, contiguous, taken as they
+    are) -> (loss 0-d, wsum [1], stats [2, B Q] = (row max, log sum exp(x - max)), target int32
+    [B Q]); moff / toff int32 [B + 1] on the device, rows_all / cols_all / labels int64."""
+    w = weight.detach().float().contiguous()
+    _need_cuda(logits, w, rows_all, cols_all, moff, toff, labels)
+    B, Q, C1 = logits.shape
+    dev = logits.device
+    L = _lib.lib()
+    N = B * Q
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    wsum = torch.empty((1,), dtype=torch.float32, device=dev)
+    stats = torch.empty((2, N), dtype=torch.float32, device=dev)
+    target = torch.empty((N,), dtype=torch.int32, device=dev)
+    ws = _workspace(dev, L.rgbd_class_loss_workspace_size(B, Q, C1), "class_loss")
+    code = RGBD_BF16 if logits.dtype == torch.bfloat16 else RGBD_F32
+    check(L.rgbd_class_loss_fwd(code, _p(logits), _p(w), B, Q, C1, _p(rows_all), _p(cols_all), rows_all.numel(),
+                                _p(moff), _p(toff), _p(labels), labels.numel(), _p(ws), _p(loss), _p(wsum), _p(stats),
+                                _p(target), _stream(dev)), "rgbd_class_loss_fwd")
+    return loss, wsum, stats, target
+
+
+class _ClassLoss(torch.autograd.Function):
+    """(logits [B, Q, C1], class weights, the matches) -> the weighted cross-entropy of every row
+    against its matched target's class, no object elsewhere (loss_labels :548-578)."""
+
+    @staticmethod
+    def forward(ctx, logits, weight, rows_all, cols_all, moff, toff, labels):
+        x = logits.detach()
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        x = x.contiguous()  # bf16 goes to the kernel as it is: no float32 copy
+        loss, wsum, stats, target = class_loss_forward(x, weight, rows_all, cols_all, moff, toff, labels)
+        ctx.save_for_backward(x, weight, stats, target, wsum)
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, stats, target, wsum = ctx.saved_tensors
+        B, Q, C1 = x.shape
+        g = g.detach().float().contiguous()
+        w = weight.detach().float().contiguous()
+        gx = torch.empty_like(x)
+        code = RGBD_BF16 if x.dtype == torch.bfloat16 else RGBD_F32
+        check(_lib.lib().rgbd_class_loss_bwd(code, _p(x), _p(w), B, Q, C1, _p(stats), _p(target), _p(wsum), _p(g),
+                                             _p(gx), _stream(x.device)), "rgbd_class_loss_bwd")
+        return gx.to(ctx.dtype), None, None, None, None, None, None
+
+
+def class_loss(logits, weight, indices: LsaResult, class_labels):
+    """``nn.CrossEntropyLoss(weight)(logits.transpose(1, 2), target_classes)`` of
+    Mask2FormerLoss.loss_labels (:548-578) as a 0-d float32 tensor, differentiable in ``logits``
+    [B, Q, C1]: image b's query ``rows[m]`` gets the class ``class_labels[b][cols[m]]`` for every
+    match of ``indices`` (the batched assignment's LsaResult), every other query the last class.
+    The per-image match and target offsets are cached device constants (no blocking copy)."""
+    if not (isinstance(indices, LsaResult) and indices.rows_all is not None):
+        raise TypeError("class_loss takes the batched assignment's LsaResult (rows_all / cols_all / counts)")
+    B = logits.shape[0]
+    if len(indices.counts) != B or len(class_labels) != B:
+        raise ValueError(f"class_loss: {B} images, {len(indices.counts)} match counts, {len(class_labels)} label sets")
+    dev = logits.device
+    moff = device_vec(_offsets(indices.counts), torch.int32, dev)
+    toff = device_vec(_offsets(c.numel() for c in class_labels), torch.int32, dev)
+    return _ClassLoss.apply(logits, weight, indices.rows_all.long(), indices.cols_all.long(), moff, toff,
+                            labels_all(class_labels, dev))
+
+
 def match_costs(matcher, masks_queries_logits, class_queries_logits, mask_labels, class_labels):
     """The matcher's cost matrices of every image ([Q, T_b] each), as
     Mask2FormerHungarianMatcher.forward builds them (:445-470): one ``torch.rand(1, P, 2)`` per
@@ -319,10 +408,17 @@ class HipMask2FormerLoss(Mask2FormerLoss):
     def loss_labels(self, class_queries_logits, class_labels, indices):
         """Mask2FormerLoss.loss_labels (:548-578) with the matched targets' classes gathered from
         the concatenated labels in one index (the reference: one gather per image + cat) and
-        scattered into the no-object fill by flat index (the matches are distinct)."""
+        scattered into the no-object fill by flat index (the matches are distinct).  With
+        HIP_CLASS_LOSS (the default) the target build and the cross-entropy are ``class_loss``."""
         if not (isinstance(indices, LsaResult) and indices.rows_all is not None):
             return super().loss_labels(class_queries_logits, class_labels, indices)
         pred_logits = class_queries_logits
+        if (HIP_CLASS_LOSS and pred_logits.is_cuda and pred_logits.dim() == 3
+                and 2 <= pred_logits.shape[-1] <= class_loss_max_classes() and 0 < pred_logits.numel() < 1 << 31):
+            # one kernel of our own for the target build, the softmax and the weighted mean (fixed
+            # reduction order: no deterministic-mode branch); more classes than it holds take the
+            # torch path below
+            return {"loss_cross_entropy": class_loss(pred_logits, self.empty_weight, indices, class_labels)}
         batch_size, num_queries, _ = pred_logits.shape
         criterion = nn.CrossEntropyLoss(weight=self.empty_weight)
         dev = pred_logits.device

@@ -5,7 +5,9 @@ instances), random-init weights.  Two arms on the same weights and inputs:
   hip   — hot path (bf16 MFMA) + f1 mask predictor + f2 deformable attention + f3 matcher on HIP
   hf    — hot path (bf16 MFMA), the f1/f2/f3 modules as the installed Hugging Face code
   hip_det — the hip arm in deterministic mode (rgbd_amd.determinism: atomic-free MSDA and
-          point-sample backward, 1-d class loss); "--arms hip,hip_det" times both modes in one process
+          point-sample backward); "--arms hip,hip_det" times both modes in one process
+  hip_atence — the hip arm with point_loss.HIP_CLASS_LOSS off: the loss's class cross-entropy on
+          torch's target build + nn.CrossEntropyLoss, as before csrc/class_loss.hip
 with the HF parts in float32 or under torch.autocast(bfloat16) (--amp).  Prints one JSON line.
 --clip X: the arms step with HipAdamW(**HF_TRAINER_ADAMW, max_grad_norm=X), the Trainer's AdamW
 with its global-norm clip on the device, and report the last step's gradient
@@ -71,6 +73,9 @@ def main():
                 elif type(mod) is dense._FusedReLU:
                     mod.__class__ = torch.nn.ReLU
         mode_before = determinism.get_state()
+        class_loss_before = point_loss.HIP_CLASS_LOSS
+        if arm == "hip_atence":  # A/B: the loss's class cross-entropy back on torch
+            point_loss.HIP_CLASS_LOSS = False
         if arm == "hip_det":
             determinism.set_deterministic(True)
         params = [p for p in m.parameters() if p.requires_grad]
@@ -102,6 +107,7 @@ def main():
                     "grad_norm": None if clip is None else round(float(opt.grad_norm), 4)}
         del m, opt
         determinism.set_deterministic(mode_before)
+        point_loss.HIP_CLASS_LOSS = class_loss_before
         torch.cuda.empty_cache()
     if "hip" in res and "hf" in res:
         res["speedup_hip_vs_hf_modules"] = round(res["hip"]["img_s"] / res["hf"]["img_s"], 3)
