@@ -144,11 +144,6 @@ struct MtTable {
       hi__ = mid__ - 1;                      \
   }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // the workgroup's 256 values summed in a fixed tree (xor butterflies within a wave, then the four
 // wave sums in wave order); the result is valid in thread 0
 __device__ __forceinline__ double block_sum_f64(double v) {

@@ -90,6 +90,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // Hide a loop-invariant pointer from LICM: without it hipcc hoists every weight-fragment load
 // of a persistent tile loop out of the loop and spills them all to scratch.

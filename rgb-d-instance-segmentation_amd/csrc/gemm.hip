@@ -663,7 +663,7 @@ __global__ __launch_bounds__(256) void k_colsum(const T* __restrict__ y, int row
 }
 
 // ---- bf16, both operands K-contiguous (forward: X [M][K] W [N][K]; dX with the weight
-// transposed), batch 1, no split: the conv5 recipe (ratio.hip k_rp_conv3x3_v3) on a plain
+// transposed), batch 1, no split: the conv5 recipe (ratio_conv5.hip k_rp_conv5_v4) on a plain
 // GEMM.  512 threads = 8 waves as 2 (M) x 4 (N), wave tile (TM/2) x (TN/4); K staged 64 at a
 // time (128-byte rows, 16-byte chunk c at slot c ^ (row & 7)) by LDS-DMA straight from global
 // memory (global_load_lds_dwordx4: no VGPR staging, no ds_write) into an S-stage ring issued

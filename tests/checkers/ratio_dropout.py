@@ -1,5 +1,5 @@
 """Replay of the ratio predictor's train-mode dropout stream (include/rgbd_hip.h, the comment
-above `rgbd_ratio_forward`; `hash_uniform`, `k_rp_tail_fc1` and `k_rp_tail_head` in csrc/ratio.hip),
+above `rgbd_ratio_forward`; `hash_uniform`, `k_rp_tail_fc1` and `k_rp_tail_head` in csrc/ratio_tail.hip),
 restated in Python integers and NumPy uint64:
 
     s = seed + counter                                             (mod 2^64)

@@ -31,8 +31,8 @@ def test_bench_launcher_propagates_failure():
 
 def test_bench_roofline_traffic_comes_from_the_newest_pmc_table():
     """roofline.traffic: conv5's HBM bytes from the newest committed PMC table that has it, whatever template
-    argument list the kernel's trace name carries (k_rp_conv3x3_v3<false> since the stamped
-    instantiation exists), and null for a non-default shape."""
+    argument list the kernel's trace name carries (k_rp_conv5_v4<0> today; the older tables carry
+    its predecessors' names), and null for a non-default shape."""
     sys.path.insert(0, str(REPO))
     import bench
     tables = sorted((REPO / "profiles").glob("*/pmc_traffic.json"))
