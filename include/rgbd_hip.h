@@ -638,6 +638,41 @@ int rgbd_pp_instance(const float* class_logits, const float* mask_logits, int B,
 int rgbd_pp_binary_maps(const void* ws, int B, int Q, int b, int Ht, int Wt, const int* seg_id, float* out,
                         void* stream);
 
+/* ---------------------------------------------------------------- f4b semantic / panoptic post-processing
+ * Replace Mask2FormerImageProcessor.post_process_semantic_segmentation and
+ * post_process_panoptic_segmentation (transformers 5.15 image_processing_pil_mask2former.py:587
+ * and :788, with compute_segments :162, check_segment_validity :143 and
+ * remove_low_and_no_objects :245; csrc/postprocess_dense.hip restates the arithmetic).
+ *   class_logits float32 [B][Q][C1] (C1 = classes + no-object), mask_logits float32 [B][Q][h][w];
+ *   target_h_host / target_w_host: per-image output sizes (384 x 384 for "no resize").
+ *   Caps (RGBD_E_SHAPE beyond them): C1 - 1 <= 1024 for both, Q <= 1024 for the panoptic call.
+ *   Any B: the images of one call are processed one after the other on the stream.
+ *   No float atomics: two calls on the same input give the same bits.
+ * rgbd_pp_semantic: map_host: B device pointers to int64 [Ht][Wt] class maps (argmax, the lowest
+ *   class id on a tie); scores_host: NULL, or B device pointers to float32 [C1 - 1][Ht][Wt]
+ *   (return_segmentation_scores=True).
+ *   ws: rgbd_pp_semantic_workspace_size(B, Q, C1) = align256(4 B Q C) + align256(4 C 384^2) bytes
+ *   (C = C1 - 1: the class probabilities of the call and the 384 x 384 scores of one image; it
+ *   does not grow with the target sizes).
+ * rgbd_pp_panoptic: seg_host: B device pointers to [Ht][Wt] maps of 4-byte cells: int32 segment
+ *   ids (0 = no segment) where table[b][0] > 0, float32 -1 where table[b][0] == 0 (nothing kept:
+ *   decided on the device, the caller reads the table, not the scores).
+ *   table int32 [B][1 + 5 Q] (written): the number of kept queries n, then for the kept queries
+ *   in query order id[Q] (0 = not a valid segment), label[Q], score[Q] (float32 bits), area[Q]
+ *   and orig[Q] (the counts of check_segment_validity); entries past n are 0.
+ *   fuse_mask_host: NULL (nothing fused) or 16 host words, bit c set = label c is in
+ *   label_ids_to_fuse (copied during the call).
+ *   ws: rgbd_pp_panoptic_workspace_size(B, Q) = align256(4 B Q) bytes. */
+size_t rgbd_pp_semantic_workspace_size(int B, int Q, int C1);
+int rgbd_pp_semantic(const float* class_logits, const float* mask_logits, int B, int Q, int C1, int h, int w,
+                     const int* target_h_host, const int* target_w_host, long long* const* map_host,
+                     float* const* scores_host, void* ws, void* stream);
+size_t rgbd_pp_panoptic_workspace_size(int B, int Q);
+int rgbd_pp_panoptic(const float* class_logits, const float* mask_logits, int B, int Q, int C1, int h, int w,
+                     const int* target_h_host, const int* target_w_host, double threshold, double mask_threshold,
+                     double overlap_mask_area_threshold, const unsigned long long* fuse_mask_host,
+                     void* const* seg_host, int* table, void* ws, void* stream);
+
 /* ---------------------------------------------------------------- f4 segm mAP: mask IoU
  * The mask IoU of torchmetrics MeanAveragePrecision(iou_type="segm") as the reference's
  * Evaluator uses it (model_essential_part.py:56-157; pycocotools maskApi rleIou underneath).
