@@ -199,6 +199,27 @@ typedef struct rgbd_nhwc_job_f32 {
   int dst_dtype;    /* RGBD_BF16 or RGBD_F32 */
 } rgbd_nhwc_job_f32;
 int rgbd_nchw_to_nhwc_multi_f32(int n, const rgbd_nhwc_job_f32* jobs, void* stream);  /* jobs: host array */
+/* The colour-map gradients of the hot path's end-to-end mode, one to four jobs in one launch:
+ *   out = G + D  per element, one float32 add of the widened operands and one rounding to G's
+ *   dtype (bitwise (G.float() + D_as_nchw.float()).to(G.dtype) in torch); d == NULL: out = G + G.
+ * G and out are [B][C][H][W] in g_dtype; D is the cascade gradient in d_dtype, [B][C][H][W]
+ * (d_nhwc == 0) or [B][H][W][C] (d_nhwc != 0; through an LDS tile transpose; C % 8 == 0,
+ * RGBD_E_SHAPE otherwise).  16-byte accesses where the pointers are 16-byte aligned (and, with an
+ * NHWC source, H W % 8 == 0); element-wise with the same bits otherwise.  No workspace, no
+ * atomics, no synchronisation.  A job with B C H W == 0 is skipped; when no job has work nothing
+ * is launched.  Checked before any HIP call: n outside [1, 4], jobs / g / out NULL or a negative
+ * size: RGBD_E_ARG; a dtype code other than RGBD_F32 / RGBD_BF16 (d_dtype only with d):
+ * RGBD_E_DTYPE; B C H W >= 2^31: RGBD_E_SHAPE. */
+typedef struct rgbd_color_grad_job {
+  const void* g;    /* [B][C][H][W] g_dtype (device) */
+  const void* d;    /* d_dtype, NCHW or NHWC (device), or NULL */
+  void* out;        /* [B][C][H][W] g_dtype (device) */
+  int B, C, H, W;
+  int g_dtype;      /* RGBD_F32 or RGBD_BF16 */
+  int d_dtype;      /* RGBD_F32 or RGBD_BF16 (ignored when d is NULL) */
+  int d_nhwc;       /* 0: d is [B][C][H][W]; otherwise [B][H][W][C] */
+} rgbd_color_grad_job;
+int rgbd_color_grads(int n, const rgbd_color_grad_job* jobs, void* stream);  /* jobs: host array */
 /* Packs DSAModule weights (conv_layers[0..3].weight, rgb_projection.weight; float32
  * [4][Cout][Cin][3][3] and [Cout][Cin][3][3]) into the implicit-GEMM B operands.
  * RGBD_F32 (segment form):

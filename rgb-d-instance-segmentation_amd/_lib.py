@@ -65,6 +65,7 @@ SIGNATURES = {
     "rgbd_nchw_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "rgbd_nchw_to_nhwc_multi": (_I, [_I, _P, _P]),
     "rgbd_nchw_to_nhwc_multi_f32": (_I, [_I, _P, _P]),
+    "rgbd_color_grads": (_I, [_I, _P, _P]),
     "rgbd_adamw_multi": (_I, [_I, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, ctypes.c_double, _P]),
     "rgbd_adamw_multi_shadow": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,

@@ -11,6 +11,7 @@ the loss's matcher costs, assignment and point-sampled mask terms (f3), and ever
 (conv.HipConv2d: the pixel decoder's 1x1 input projections and mask projection, the FPN 3x3 and
 Swin's 4x4 patch embedding as MFMA GEMMs, forward and backward).
 """
+import contextlib
 import random
 
 import numpy as np
@@ -60,6 +61,9 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
         # None: the hot path's colour maps / cp1 / features in the compute dtype; torch.float32 with
         # bf16 compute: the float32-interface mode (hot_path.float32_interface)
         self.interface_dtype = None
+        # False: the reference's detached colour maps (Q1; the encoder takes no gradient).  True:
+        # the opt-in end-to-end mode (set_end_to_end); 0.0.0 ignores it
+        self.end_to_end = False
         if version == "0.4.0":
             self.ratio_predictor = EnhancedDepthImageRatioPredictor(3)
             self.dsam0 = DSAModule(in_channels=96, out_channels=192, num_depth_regions=3)
@@ -76,18 +80,21 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
                 m.compute_dtype = dtype
         return self
 
-    def hot_path_features(self, pixel_values: Tensor, color_feature_map, ratios=None, status_sink=None):
+    def hot_path_features(self, pixel_values: Tensor, color_feature_map, ratios=None, status_sink=None,
+                          color_grads=False):
         """custom_model.py:325-355 on the HIP kernels: returns the 4 backbone features.
-        ``status_sink``: see hot_path.hot_path (None = raise the reference's ValueError at once)."""
+        ``status_sink``: see hot_path.hot_path (None = raise the reference's ValueError at once).
+        ``color_grads``: hot_path's end-to-end mode (the colour maps take gradients)."""
         # the ratio-free part (decomposition modes, bf16 colour layouts) beside the ratio predictor
         prep = prepare(pixel_values, list(color_feature_map), self.compute_dtype,
-                       dsam_modules=[self.dsam0, self.dsam1, self.dsam2], interface_dtype=self.interface_dtype)
+                       dsam_modules=[self.dsam0, self.dsam1, self.dsam2], interface_dtype=self.interface_dtype,
+                       color_grads=color_grads)
         if ratios is None:
             ratios = self.ratio_predictor(pixel_values[:, 3:6])       # :336 (no grad, Q2)
         feats = hot_path(pixel_values, ratios, list(color_feature_map), [self.dsam0, self.dsam1, self.dsam2],
                          self.depth_gradient_injection, dtype=self.compute_dtype,
                          check_status=status_sink is None, status_sink=status_sink, prepared=prep,
-                         interface_dtype=self.interface_dtype)
+                         interface_dtype=self.interface_dtype, color_grads=color_grads)
         dt = color_feature_map[0].dtype
         return [f.to(dt) for f in feats]
 
@@ -104,10 +111,14 @@ class CustomMask2FormerPixelLevelModule(Mask2FormerPixelLevelModule):
             rgb = pixel_values[:, 0:3, :, :]
             # :330 — Swin-T on the HIP layers (f2).  Its maps are detached at :332-333 (Q1), so no
             # graph is recorded for it: identical values, the fused forward-only kernels apply.
-            with torch.no_grad():
+            # End-to-end mode (opt-in, a departure from Q1): the encoder records its graph and the
+            # maps go to the hot path undetached, which returns their gradients.
+            e2e = self.end_to_end and torch.is_grad_enabled()
+            with contextlib.nullcontext() if e2e else torch.no_grad():
                 color_feature_map = self.encoder(rgb).feature_maps
             statuses = []
-            backbone_features = self.hot_path_features(pixel_values, color_feature_map, status_sink=statuses)
+            backbone_features = self.hot_path_features(pixel_values, color_feature_map, status_sink=statuses,
+                                                       color_grads=e2e)
         with ops.host_constants():  # the pixel decoder's level-shape tensor (modeling_mask2former.py:1347)
             decoder_output = self.decoder(backbone_features, output_hidden_states=output_hidden_states)
         if self.version != "0.0.0":
@@ -166,4 +177,12 @@ class CustomMask2FormerForUniversalSegmentation(Mask2FormerForUniversalSegmentat
 
     def set_compute_dtype(self, dtype, interface=None):
         self.model.pixel_level_module.set_compute_dtype(dtype, interface)
+        return self
+
+    def set_end_to_end(self, flag=True):
+        """Opt into (or out of) the end-to-end mode of the paper model: the Swin encoder is no
+        longer run under no_grad and its four maps take gradients through the fused hot path
+        (DESIGN.md §5.17).  The default, False, is the reference's behaviour: detached colour maps
+        (Q1), so no encoder parameter receives a gradient.  version="0.0.0" ignores the flag."""
+        self.model.pixel_level_module.end_to_end = bool(flag)
         return self

@@ -14,6 +14,10 @@ Here:
     DGGM gate + final sum in one elementwise pass over all four scales (K2, one launch).
 Backward produces exactly the gradients the reference graph has: DSAM / DGGM parameters,
 nothing for the colour maps (detached) or the ratio (left the graph via .item()).
+``color_grads=True`` is the opt-in end-to-end mode, a deliberate departure from
+Q1: the cascade gradient continues through dsam0 and one launch forms the four colour-map
+gradients  d c_3 = 2 G_3,  d c_k = G_k + d cp1_k  (k < 3); forward and parameter gradients are
+bitwise those of the default mode.
 Three precision modes: float32; bfloat16 (operands, cp1 and features bf16); and bfloat16 compute
 with a float32 interface (``interface_dtype=torch.float32``: colour maps, cp1 and features float32,
 bf16 only as the DSAM operands; ``float32_interface``).
@@ -171,9 +175,10 @@ def _sources(pixel_values, colors):
 PREPACK = (0, 1)
 
 
-def _pack_all(m, k, dtype):
+def _pack_all(m, k, dtype, color_grads=False):
     conv_ws = [m.conv_layers[i].weight for i in range(4)]
-    want_bwd = k > 0 and torch.is_grad_enabled() and m.rgb_projection.weight.requires_grad
+    # dsam0's input takes a gradient in the end-to-end mode only
+    want_bwd = (k > 0 or color_grads) and torch.is_grad_enabled() and m.rgb_projection.weight.requires_grad
     return m._pack_cache.get(conv_ws, m.rgb_projection.weight, dtype, code_mask=None, want_bwd=want_bwd)
 
 
@@ -192,14 +197,16 @@ def float32_interface(dtype, interface_dtype):
     return dtype == torch.bfloat16
 
 
-def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_modules=None, interface_dtype=None):
+def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_modules=None, interface_dtype=None,
+            color_grads=False):
     """Launch the ratio-independent part of the hot path (call it before the ratio predictor,
     pass the result to ``hot_path(..., prepared=)``).  bf16 on the GPU: on the side stream
     (``overlap`` False: on the current stream).  With ``dsam_modules`` (bf16) the filters of the
     PREPACK DSAMs are packed here too, from the parameters as they are now (after the previous
     optimizer step).  ``interface_dtype``: see ``float32_interface``; torch.float32 with bf16 keeps
     the colour maps float32 (one launch writes colour 0's bf16 NHWC operand and the float32 NHWC
-    residuals of colours 1-3)."""
+    residuals of colours 1-3).  ``color_grads``: as given to ``hot_path`` (dsam0's backward filters
+    are then packed here too; a Prepared built without them is repacked by the forward)."""
     f32io = float32_interface(dtype, interface_dtype)
     pv = pixel_values.detach().float().contiguous()
     cols = [c.detach().to(torch.float32 if f32io else dtype).contiguous() for c in colors]
@@ -216,7 +223,7 @@ def prepare(pixel_values, colors, dtype=torch.float32, overlap=True, dsam_module
         packs = {}
         if bf16 and dsam_modules is not None:
             for k in PREPACK:
-                packs[k] = _pack_all(dsam_modules[k], k, dtype)
+                packs[k] = _pack_all(dsam_modules[k], k, dtype, color_grads)
         held["packs"] = packs
         return [m.info, m.ws, m.masks, nhwc, [t for pk in packs.values() for t in pk if t is not None]]
     _, _, _, nhwc, _ = side.run(work, pv, *cols)
@@ -256,7 +263,10 @@ class HotPathFunction(torch.autograd.Function):
             ops.raise_on_status(info)
         if cfg.get("status_sink") is not None:
             cfg["status_sink"].append(ops.DeferredStatus(info))
-        training = any(ctx.needs_input_grad[7:])
+        # end-to-end mode: some colour map takes a gradient (the whole backward then runs)
+        cg = bool(cfg.get("color_grads")) and any(ctx.needs_input_grad[3:7])
+        training = any(ctx.needs_input_grad[7:]) or cg
+        dx_ks = (1, 2, 0) if cg else (1, 2)  # the DSAMs whose input takes a gradient
         chans = [(colors[k].shape[1], colors[k + 1].shape[1]) for k in range(3)]
         conv_plans = dw_plans = None
         if bf16:
@@ -264,16 +274,17 @@ class HotPathFunction(torch.autograd.Function):
             # forward and dX legs by two launches here, the dW legs on the side stream below
             legs = [(ops.LEG_FWD, codes[k], *chans[k]) for k in range(3)]
             if training:
-                legs += [(ops.LEG_DX, codes[k], *chans[k]) for k in (1, 2)]
+                legs += [(ops.LEG_DX, codes[k], *chans[k]) for k in dx_ks]
             conv_plans = ops.dsam_plan(legs)
 
         def pack(k):
             pre = prepared.packs.get(k)
-            if pre is not None and (pre[1] is not None or not (training and k > 0)):
+            want_bwd = training and k in dx_ks  # dsam0's input takes a gradient in the end-to-end mode only
+            if pre is not None and (pre[1] is not None or not want_bwd):
                 return pre  # packed for all codes beside the ratio predictor
             return cfg["pack_cache"][k].get(dsam_p[k][0:8:2], dsam_p[k][8], dtype,
                                             code_mask=None if masks is None else masks[k:k + 1],
-                                            want_bwd=training and k > 0)  # dsam0's input takes no gradient
+                                            want_bwd=want_bwd)
         cp1 = [colors[0]]
         if bf16:
             packs = [pack(0)]
@@ -327,7 +338,8 @@ class HotPathFunction(torch.autograd.Function):
             outs = ops.dggm_fuse_fwd_multi(cp1, colors, pixel_values, dggm_p[0::2], dggm_p[1::2], cp1_nhwc=cp1_nhwc)
         side.join()  # the dW plans, DGGM scales 0-2
         ctx.cfg = cfg
-        ctx.dx_plans = {1: conv_plans[3], 2: conv_plans[4]} if conv_plans and training else {}
+        ctx.dx_plans = {k: conv_plans[3 + i] for i, k in enumerate(dx_ks)} if conv_plans and training else {}
+        ctx.color_grads = cg
         ctx.dw_plans = dw_plans
         ctx.codes = codes
         ctx.info = info
@@ -369,10 +381,13 @@ class HotPathFunction(torch.autograd.Function):
         # bf16: the three upstream gradients the cascade reads in NHWC, converted by one launch
         # (float32 interface: the same launch rounds them, float32 NCHW -> bf16 NHWC; the DGGM
         # backward takes them in float32)
+        # end-to-end mode: G[0], dsam0's dX residual, joins the same launch
+        cg = ctx.color_grads
+        g_ks = (3, 2, 1, 0) if cg else (3, 2, 1)
         if ctx.f32io:
-            g_nhwc = dict(zip((3, 2, 1), ops.nchw_to_nhwc_multi_f32([G[3], G[2], G[1]], [torch.bfloat16] * 3)))
+            g_nhwc = dict(zip(g_ks, ops.nchw_to_nhwc_multi_f32([G[k] for k in g_ks], [torch.bfloat16] * len(g_ks))))
         else:
-            g_nhwc = dict(zip((3, 2, 1), ops.nchw_to_nhwc_multi([G[3], G[2], G[1]]))) if bf16 else {}
+            g_nhwc = dict(zip(g_ks, ops.nchw_to_nhwc_multi([G[k] for k in g_ks]))) if bf16 else {}
         dcp_nhwc = g_nhwc[3] if bf16 else ops.nchw_to_nhwc(dcp)
         grads_dsam = [None, None, None]
         def dsam_dw(k, dcp, dcp_nhwc):
@@ -396,7 +411,9 @@ class HotPathFunction(torch.autograd.Function):
             if bf16:
                 return ops.dsam_bwd_data(dcp_nhwc, ctx.codes[k], ctx.packs[k][1], None, want_nhwc=True,
                                          want_nchw=False, gin_nhwc=g_nhwc[k], plan=ctx.dx_plans.get(k))
-            return ops.dsam_bwd_data(dcp_nhwc, ctx.codes[k], ctx.packs[k][1], G[k], want_nhwc=(k > 1))
+            # float32: the next dX leg reads the NHWC copy (dsam0's only in the end-to-end mode)
+            return ops.dsam_bwd_data(dcp_nhwc, ctx.codes[k], ctx.packs[k][1], G[k],
+                                     want_nhwc=(k > 1 or (cg and k == 1)))
         # dW2 beside the cascade; dX2, dX1, then dW1 and dW0 on the main stream (the side stream
         # already carries the DGGM backward, dW2 and, with in-backward optimizer steps, the
         # dsam2 update)
@@ -404,6 +421,17 @@ class HotPathFunction(torch.autograd.Function):
         grads_dsam[2] = side.run(lambda: dsam_dw(2, dcp, dcp_nhwc), dcp_nhwc, ctx.x_nhwc[2], ctx.codes[2], ctx.info)
         dcp1, dcp1_nhwc = dsam_dx(2, dcp, dcp_nhwc)
         dcp0, dcp0_nhwc = dsam_dx(1, dcp1, dcp1_nhwc)
+        cgrads = [None] * 4
+        if cg:
+            # end-to-end mode, on the main stream (no further fork: _Side): the cascade continues
+            # through dsam0, then one launch forms d c_3 = 2 G_3 and d c_k = G_k + d cp1_k (k < 3)
+            # from the cascade gradients in the layout the dX legs left them in
+            dcpi, dcpi_nhwc = dsam_dx(0, dcp0, dcp0_nhwc)
+            D = [dcpi_nhwc, dcp0_nhwc, dcp1_nhwc, None] if bf16 else [dcpi, dcp0, dcp1, None]
+            dc = ops.color_grads(G, D, nhwc=(0, 1, 2) if bf16 else ())
+            cgrads = [d.to(dt) if need else None for d, dt, need in zip(dc, ctx.in_dtypes, ctx.needs_input_grad[3:7])]
+            if not bf16:
+                dcp0_nhwc = None  # dW0 takes the NCHW gradient alone, as in the default mode
         if bf16 and JOINT_DW and ctx.dw_plans:
             # dW1 and dW0 are ready together: their GEMMs share one launch (two whole-chip launches
             # queue behind each other and each drains on a partly idle chip)
@@ -418,11 +446,12 @@ class HotPathFunction(torch.autograd.Function):
                                      ctx.info)
             grads_dsam[0] = dsam_dw(0, dcp0, dcp0_nhwc)  # the last launches of the backward, the join after them
         pgrads = grads_dsam[0] + grads_dsam[1] + grads_dsam[2] + grads_dggm
-        return (None, None, None, None, None, None, None, *pgrads)
+        return (None, None, None, *cgrads, *pgrads)
 
 
 def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch.float32, check_status=False,
-             grad_hook=None, status_sink=None, prepared=None, overlap=True, overlap_bwd=True, interface_dtype=None):
+             grad_hook=None, status_sink=None, prepared=None, overlap=True, overlap_bwd=True, interface_dtype=None,
+             color_grads=False):
     """Run the fused hot path.  ``dsam_modules``: the three DSAModule instances;
     ``dggm_module``: the DepthGradientInjectionResidual instance.  ``check_status`` raises the
     reference's ValueError for a degenerate depth histogram right away (synchronising);
@@ -442,8 +471,18 @@ def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch
     ``dtype=torch.bfloat16`` = the float32-interface mode (colour maps read, cp1 kept and features
     returned in float32, gradients taken in float32; bf16 only as the DSAM operands: DESIGN.md
     §5.11); torch.float32 with ``dtype=torch.float32`` is the float32 mode.  Anything else raises
-    ValueError.  A ``prepared`` must have been built with the same value."""
+    ValueError.  A ``prepared`` must have been built with the same value.
+    ``color_grads`` True: the end-to-end mode.  Colour maps that require a
+    gradient receive one (d c_3 = 2 G_3, d c_k = G_k + d cp1_k with the cascade continued through
+    dsam0), in their own dtypes; outputs and parameter gradients are bitwise the default mode's.
+    False (the reference's behaviour, Q1), or no colour map requiring a gradient: today's launches,
+    no colour gradient.  Not with ``grad_hook``: the hook's groups are the hot path's own
+    parameters, so the encoder's gradients would stay un-reduced on every rank (ValueError)."""
     float32_interface(dtype, interface_dtype)
+    if color_grads and grad_hook is not None:
+        raise ValueError("hot_path: color_grads=True with a grad_hook: the overlapped reducer's groups "
+                         "(distributed.hot_path_grad_groups) do not hold the encoder's parameters, whose gradients "
+                         "would not be all-reduced; reduce the whole model with torch DistributedDataParallel instead")
     params = []
     for m in dsam_modules:
         for i in range(4):
@@ -454,7 +493,7 @@ def hot_path(pixel_values, ratio, colors, dsam_modules, dggm_module, dtype=torch
         params += [conv.weight, conv.bias]
     cfg = {"dtype": dtype, "check_status": check_status, "grad_hook": grad_hook, "status_sink": status_sink,
            "pack_cache": [m._pack_cache for m in dsam_modules], "overlap": overlap, "overlap_bwd": overlap_bwd,
-           "prepared": prepared, "interface_dtype": interface_dtype}
+           "prepared": prepared, "interface_dtype": interface_dtype, "color_grads": bool(color_grads)}
     if prepared is not None:
         prepared.check(pixel_values, colors)
     pv = prepared.pixel_values if prepared is not None else pixel_values.detach().float().contiguous()

@@ -513,6 +513,37 @@ def nchw_to_nhwc_multi_f32(xs, out_dtypes):
     return ys
 
 
+class _ColorGradJob(ctypes.Structure):  # rgbd_color_grad_job
+    _fields_ = [("g", ctypes.c_void_p), ("d", ctypes.c_void_p), ("out", ctypes.c_void_p), ("B", ctypes.c_int),
+                ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("g_dtype", ctypes.c_int),
+                ("d_dtype", ctypes.c_int), ("d_nhwc", ctypes.c_int)]
+
+
+def color_grads(G_list, D_list, nhwc=(), out=None):
+    """The hot path's colour-map gradients, one to four in one launch (rgbd_color_grads):
+    ``out[i] = G_list[i] + D_list[i]`` in G's dtype and NCHW layout, one float32 add and one
+    rounding per element; ``D_list[i]`` None gives ``G + G``.  G is [B,C,H,W] float32 or bfloat16;
+    D float32 or bfloat16, [B,C,H,W], or [B,H,W,C] for the indices listed in ``nhwc``.  ``out``:
+    tensors to write (shaped and typed like G), else new ones."""
+    n = len(G_list)
+    if not 1 <= n <= 4 or len(D_list) != n or (out is not None and len(out) != n):
+        raise ValueError("color_grads: one to four gradients, one D (or None) and one output each")
+    outs = [torch.empty_like(g) for g in G_list] if out is None else list(out)
+    _need_cuda(*G_list, *D_list, *outs)
+    arr = (_ColorGradJob * n)()
+    for i, (g, d, o) in enumerate(zip(G_list, D_list, outs)):
+        if g.dim() != 4 or o.shape != g.shape or o.dtype != g.dtype:
+            raise ValueError("color_grads: G is [B,C,H,W]; out has G's shape and dtype")
+        B, C, H, W = g.shape
+        if d is not None and tuple(d.shape) != ((B, H, W, C) if i in nhwc else (B, C, H, W)):
+            raise ValueError(f"color_grads: D[{i}] {tuple(d.shape)} does not match G {tuple(g.shape)}"
+                             f"{' in NHWC' if i in nhwc else ''}")
+        arr[i] = _ColorGradJob(g.data_ptr(), None if d is None else d.data_ptr(), o.data_ptr(), B, C, H, W,
+                               _dtype_code(g), 0 if d is None else _dtype_code(d), int(d is not None and i in nhwc))
+    check(_lib.lib().rgbd_color_grads(n, arr, _stream(G_list[0].device)), "rgbd_color_grads")
+    return outs
+
+
 def dsam_code_masks(codes):
     """codes: list of uint8 region-code maps -> uint32 device tensor [len(codes)], bit k set when
     code k occurs in map i (the codes the bf16 packed filters are needed for)."""

@@ -12,7 +12,9 @@ with the HF parts in float32 or under torch.autocast(bfloat16) (--amp).  Prints 
 --clip X: the arms step with HipAdamW(**HF_TRAINER_ADAMW, max_grad_norm=X), the Trainer's AdamW
 with its global-norm clip on the device, and report the last step's gradient
 norm; an arm named "<arm>:noclip" keeps the default optimizer (torch's fused AdamW, no clip), so
-"--arms hip:noclip,hip --clip 1.0" times both in one process."""
+"--arms hip:noclip,hip --clip 1.0" times both in one process.  An arm named "<arm>:e2e" runs the
+opt-in end-to-end mode (set_end_to_end(True), DESIGN.md §5.17: the Swin backbone trains through
+the fused hot path), so "--arms hip,hip:e2e" reports the cost of the mode."""
 import argparse
 import json
 import sys
@@ -51,13 +53,15 @@ def main():
     res = {"batch": B, "shape": f"{W}x{H}", "amp_bf16": bool(args.amp), "clip": args.clip}
     for ai, name in enumerate(args.arms.split(",")):
         arm, _, flag = name.partition(":")
-        if flag not in ("", "noclip"):
+        if flag not in ("", "noclip", "e2e"):
             raise SystemExit(f"unknown arm suffix in {name!r}")
         clip = None if flag == "noclip" else args.clip
         torch.manual_seed(0)
         m = CustomMask2FormerForUniversalSegmentation(standard_config(48), version="0.4.0")
         winit.init_deterministic(m)
         m.set_compute_dtype(torch.bfloat16).to(dev).train()
+        if flag == "e2e":
+            m.set_end_to_end(True)
         if arm == "hf":
             mask_predictor.uninstall(m)
             masked_attention.uninstall(m)
@@ -104,6 +108,7 @@ def main():
         key = name if name not in res else f"{name}_{ai}"
         res[key] = {"img_s": round(B / dt, 2), "ms_per_step": round(dt * 1e3, 1), "loss": round(float(loss.detach()), 4),
                     "deterministic": determinism.is_deterministic(), "clip": clip,
+                    "end_to_end": flag == "e2e",
                     "grad_norm": None if clip is None else round(float(opt.grad_norm), 4)}
         del m, opt
         determinism.set_deterministic(mode_before)
