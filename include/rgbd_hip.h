@@ -694,6 +694,34 @@ int rgbd_pp_panoptic(const float* class_logits, const float* mask_logits, int B,
                      double overlap_mask_area_threshold, const unsigned long long* fuse_mask_host,
                      void* const* seg_host, int* table, void* ws, void* stream);
 
+/* ---------------------------------------------------------------- f5 overlay: a prediction painted over its frame
+ * The last step of the reference's visualisation (mask2former/predictor.py:295-330
+ * _create_gt_overlay_with_consistent_colors, :1286-1320 _create_prediction_overlay): the pixels of
+ * every segment blended with the segment's colour, on the device.
+ * rgbd_overlay_lut: the per-image table from segment id to colour, built from the arrays
+ *   rgbd_pp_instance writes (seg_id, topk_idx: int32 [B][Q]).  lut int32 [B][n_ids] (OVERWRITTEN):
+ *   r | g << 8 | b << 16, or -1 = leave the pixel alone.  Every entry starts at -1; for each slot j
+ *   with 0 <= seg_id[b][j] < n_ids the entry seg_id[b][j] takes palette[k % n_colors] (palette
+ *   uint8 [n_colors][3]), k = topk_idx[b][j] % C (the label) with color_by 0, the segment id with
+ *   color_by 1; of two slots naming one id the later decides.  Another color_by: RGBD_E_ARG;
+ *   B > 65535 or B n_ids >= 2^31: RGBD_E_SHAPE.
+ * rgbd_overlay_blend: rgb and out uint8 [B][H][W][3], seg [B][H][W] cells of seg_dtype RGBD_F32
+ *   (the instance map: a cell names an id when it holds that integer exactly; -1 = none) or
+ *   RGBD_I32 (panoptic / semantic ids); another code: RGBD_E_DTYPE.  A pixel whose id lies in
+ *   [0, n_ids) with lut[b][id] >= 0 gets, per channel, in float32
+ *     v = fl(fl(1 - alpha) * x + fl(alpha * colour))     product and sum rounded separately
+ *   clamped to [0, 255] and truncated toward zero (NumPy 2's arithmetic for the reference's
+ *   expression, bit for bit); every other pixel is copied.  rgb, seg and out may have any byte
+ *   alignment (16-byte accesses when all three are 16-byte aligned, byte accesses otherwise);
+ *   lut is 4-byte aligned.  out overlapping rgb, or a non-finite alpha: RGBD_E_ARG;
+ *   B H W > 2^36 or B n_ids >= 2^31: RGBD_E_SHAPE.
+ * Both: a NULL pointer or a non-positive size: RGBD_E_ARG, checked before any HIP call. */
+#define RGBD_I32 2
+int rgbd_overlay_lut(const int* seg_id, const int* topk_idx, int B, int Q, int C, const uint8_t* palette, int n_colors,
+                     int color_by, int32_t* lut, int n_ids, void* stream);
+int rgbd_overlay_blend(const uint8_t* rgb, const void* seg, int seg_dtype, const int32_t* lut, int B, int H, int W,
+                       int n_ids, double alpha, uint8_t* out, void* stream);
+
 /* ---------------------------------------------------------------- f4 segm mAP: mask IoU
  * The mask IoU of torchmetrics MeanAveragePrecision(iou_type="segm") as the reference's
  * Evaluator uses it (model_essential_part.py:56-157; pycocotools maskApi rleIou underneath).

@@ -13,9 +13,12 @@ in eval mode, with the dataloader's 10-channel assembly (dataloader.py:386-425) 
 The Swin colour features are inputs (``colors``), as in the module (they come from the encoder,
 outside the hot path).
 """
+import contextlib
+import ctypes
+
 import torch
 
-from . import ops
+from . import _lib, data, ops, overlay as overlay_ops
 from .graph_guard import check_and_instantiate
 from .hot_path import hot_path, prepare
 
@@ -77,3 +80,166 @@ class StreamingHotPath:
                 dst.copy_(src, non_blocking=True)
         self.graph.replay()
         return self.outs
+
+
+class StreamResult:
+    """What one ``StreamingSegmenter`` call returns.  The tensors are the segmenter's static
+    device buffers — valid once the stream reaches them, overwritten by the next call:
+
+      segmentation  float32 [B,H,W]   segment id per pixel at frame resolution, -1 = none
+      overlay       uint8 [B,H,W,3]   the frame with every kept segment painted (None without ``overlay=``)
+      seg_id, topk_idx  int32 [B,Q]   the tables of rgbd_pp_instance
+      scores        float32 [B,Q]
+
+    ``segments()`` is the only host wait."""
+
+    def __init__(self, owner, event):
+        self._owner, self._event = owner, event
+        self.segmentation = owner.segmentation
+        self.overlay = owner.overlay_u8
+        self.seg_id, self.topk_idx, self.scores = owner.seg_id, owner.topk_idx, owner.scores
+
+    def segments(self):
+        """Wait for this call's replay, raise the reference's ValueError for a frame whose depth
+        range the decomposition rejected, and return what
+        ``postprocess.post_process_instance_segmentation(..., keep_on_device=True)`` returns: per
+        image ``{"segmentation": float32 [H,W] on the device, "segments_info": [...]}``, read
+        from the pinned copy of the tables the replay made."""
+        o = self._owner
+        self._event.synchronize()
+        for st in o._statuses:
+            st.check()
+        topk_h, sid_h = o._host[0].tolist(), o._host[1].tolist()
+        ps_h = o._host[2].view(torch.float32).tolist()
+        results = []
+        for i in range(o.B):
+            segments = [{"id": sid_h[i][j], "label_id": topk_h[i][j] % o.num_labels, "was_fused": False,
+                         "score": round(ps_h[i][j], 6)}
+                        for j in range(o.Q) if sid_h[i][j] >= 0]
+            results.append({"segmentation": o.segmentation[i], "segments_info": segments})
+        return results
+
+
+class StreamingSegmenter:
+    """C5 end to end: u8 frames in, instance map, segment tables and blended overlay out, one
+    graph replay per call.
+
+    The captured path, in order: K1 assembly (``data.map_10channel``; with ``size=(S, S)`` the
+    frames are resized to the model size on the device first, non-square sizes are refused as
+    there) -> the whole drop-in model in eval mode under no_grad (``set_compute_dtype(dtype,
+    interface_dtype)``; bf16 runs under the bf16 autocast of the whole-model benchmark) ->
+    ``rgbd_pp_instance`` at the frame's (H, W), the target size ``process_prediction`` asks for ->
+    with ``overlay=dict(alpha=0.6, palette=[(r, g, b), ...], color_by="label" | "id")`` the
+    colour table and the blend (csrc/overlay.hip) -> the copy of the tables to one pinned host
+    block.  Between the frame copy and the event ``StreamResult.segments()`` waits on, nothing
+    touches the host.
+
+    ``model``: a CustomMask2FormerForUniversalSegmentation of version 0.4.0 on the GPU (put into
+    eval mode here)."""
+
+    def __init__(self, model, H, W, B=1, size=None, threshold=0.5, dtype=torch.bfloat16, interface_dtype=None,
+                 overlay=None):
+        plm = model.model.pixel_level_module
+        if getattr(plm, "version", None) != "0.4.0":
+            raise ValueError("StreamingSegmenter runs the paper model (version 0.4.0), not "
+                             f"{getattr(plm, 'version', None)!r}")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("rgbd_amd ops run on the GPU only (no CPU fallback); move the model to the GPU")
+        if size is not None:
+            size = (int(size[0]), int(size[1]))
+            if size[0] != size[1] and size != (H, W):
+                raise ValueError(f"size {size}: non-square model sizes are refused, as data.resize_frames refuses "
+                                 "them (the reference transposes their gradient planes, SURVEY Q18)")
+        self.model, self.size, self.threshold = model.eval(), size, float(threshold)
+        self.dtype, self.interface_dtype = dtype, interface_dtype
+        self.B, self.H, self.W = B, H, W
+        self.Q, self.num_labels = int(model.config.num_queries), int(model.config.num_labels)
+        self.depth_u8 = torch.zeros((B, H, W), dtype=torch.uint8, device=dev)
+        self.rgb_u8 = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=dev)
+        self.segmentation = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        self._tables = torch.zeros((3, B, self.Q), dtype=torch.int32, device=dev)
+        self.topk_idx, self.seg_id = self._tables[0], self._tables[1]
+        self.scores = self._tables[2].view(torch.float32)
+        self._host = torch.empty((3, B, self.Q), dtype=torch.int32, pin_memory=True)
+        self.overlay_cfg = None
+        self.overlay_u8 = self._lut = self._palette = None
+        if overlay is not None:
+            cfg = dict(alpha=0.6, palette=None, color_by="label")
+            unknown = set(overlay) - set(cfg)
+            if unknown:
+                raise ValueError(f"overlay: unknown keys {sorted(unknown)} (alpha, palette, color_by)")
+            cfg.update(overlay)
+            if cfg["color_by"] not in ("label", "id"):
+                raise ValueError(f"overlay color_by {cfg['color_by']!r}: 'label' or 'id' expected")
+            if cfg["palette"] is None:
+                cfg["palette"] = overlay_ops.consistent_colors(max(self.num_labels, self.Q))
+            self.overlay_cfg = cfg
+            self._palette = overlay_ops._palette(cfg["palette"], dev)
+            self._lut = torch.empty((B, self.Q), dtype=torch.int32, device=dev)
+            self.overlay_u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        self._th, self._tw = (ctypes.c_int * B)(*[H] * B), (ctypes.c_int * B)(*[W] * B)
+        self._seg_ptrs = (ctypes.c_void_p * B)(*[self.segmentation[b].data_ptr() for b in range(B)])
+        self._statuses = ()
+        self.graph = None
+        self.width = None
+
+    def _run(self):
+        self.model.set_compute_dtype(self.dtype, self.interface_dtype)
+        pv = data.map_10channel(self.rgb_u8, self.depth_u8, size=self.size)["pixel_values"]
+        amp = torch.autocast("cuda", dtype=torch.bfloat16) if self.dtype == torch.bfloat16 else contextlib.nullcontext()
+        with amp:
+            out = self.model(pixel_values=pv)
+        cls = out.class_queries_logits.to(torch.float32).contiguous()
+        masks = out.masks_queries_logits.to(torch.float32).contiguous()
+        B, Q, C1 = cls.shape
+        if (B, Q, C1 - 1) != (self.B, self.Q, self.num_labels):
+            raise RuntimeError(f"StreamingSegmenter: the model returned {tuple(cls.shape)} class logits")
+        dev = cls.device
+        L = _lib.lib()
+        st = ops._stream(dev)
+        ws = ops._workspace(dev, L.rgbd_pp_instance_workspace_size(B, Q), "postprocess")
+        _lib.check(L.rgbd_pp_instance(ops._p(cls), ops._p(masks), B, Q, C1, masks.shape[-2], masks.shape[-1], self._th,
+                                      self._tw, ctypes.c_double(self.threshold), self._seg_ptrs, ops._p(self.topk_idx),
+                                      ops._p(self.scores), ops._p(self.seg_id), ops._p(ws), st), "rgbd_pp_instance")
+        if self.overlay_cfg is not None:
+            overlay_ops.build_lut(self.seg_id, self.topk_idx, self.num_labels, self._palette,
+                                  self.overlay_cfg["color_by"], out=self._lut)
+            overlay_ops.blend(self.rgb_u8, self.segmentation, self._lut, self.overlay_cfg["alpha"], out=self.overlay_u8)
+        self._host.copy_(self._tables, non_blocking=True)
+
+    def capture(self):
+        """Two eager warm-up runs on a side stream (weight packs, workspaces, device constants),
+        then the capture on that stream; at most two concurrent branches (graph_guard)."""
+        plm = self.model.model.pixel_level_module
+        with torch.no_grad():
+            self.stream = torch.cuda.Stream()
+            self.stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self.stream):
+                for _ in range(2):
+                    self._run()
+            torch.cuda.current_stream().wait_stream(self.stream)
+            graph = torch.cuda.CUDAGraph(keep_graph=True)
+            # thread_local, as train_graph.CapturedTrainStep: a process group's watchdog thread may
+            # query events while this capture is open
+            with torch.cuda.graph(graph, stream=self.stream, capture_error_mode="thread_local"):
+                self._run()
+            # this capture's statuses: another capture of the same model replaces the module's list
+            self._statuses = tuple(getattr(plm, "captured_statuses", ()))
+            self.width = check_and_instantiate(graph, "StreamingSegmenter")
+            self.graph = graph
+        return self
+
+    def __call__(self, depth_u8=None, rgb_u8=None):
+        """Copy the frame (if given: uint8 [B,H,W] / [B,H,W,3], host or device) into the static
+        buffers without blocking, replay, record the event.  -> StreamResult."""
+        if self.graph is None:
+            self.capture()
+        if depth_u8 is not None:
+            self.depth_u8.copy_(depth_u8, non_blocking=True)
+        if rgb_u8 is not None:
+            self.rgb_u8.copy_(rgb_u8, non_blocking=True)
+        self.graph.replay()
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self.depth_u8.device))
+        return StreamResult(self, event)
