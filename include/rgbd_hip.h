@@ -722,6 +722,54 @@ int rgbd_overlay_lut(const int* seg_id, const int* topk_idx, int B, int Q, int C
 int rgbd_overlay_blend(const uint8_t* rgb, const void* seg, int seg_dtype, const int32_t* lut, int B, int H, int W,
                        int n_ids, double alpha, uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------- f6 segment matching between two label maps
+ * The step the reference's model-versus-ground-truth picture rests on (mask2former/predictor.py:181-292
+ * _create_consistent_prediction_overlay, :95-155 match_predictions_to_gt): every listed segment of a
+ * prediction map matched one-to-one, by descending IoU, to a segment of a second map — the ground
+ * truth for the comparison picture, the previous frame for stable ids in a stream.
+ * rgbd_label_contingency: a, b [B][H][W], cells of a_dtype / b_dtype RGBD_F32 | RGBD_I32 (another
+ *   code: RGBD_E_DTYPE) -> counts int32 [B][na+1][nb+1] (OVERWRITTEN): cell (i, j) = pixels naming id i
+ *   in a and id j in b, by the rule of rgbd_overlay_blend (a float32 cell names an id only when it
+ *   holds that integer exactly); index na / nb collects the cells naming no id in [0, na) / [0, nb).
+ *   Areas are the row and column sums.  Integer adds only: bitwise reproducible.  a, b, counts
+ *   4-byte aligned, else RGBD_E_ARG (16-byte loads when a and b are 16-byte aligned); na or nb > 256,
+ *   B > 65535 or H W >= 2^31: RGBD_E_SHAPE.
+ * rgbd_greedy_iou_match: counts as above, hw = H W of the maps counted; a_list int32 [B][La], b_list
+ *   [B][Lb]: segment ids in segments_info order, -1 padded.  Listed ids of area 0 (or outside the
+ *   range) are dropped; positions below are positions in the lists so filtered.  IoU = inter /
+ *   (area_a + area_b - inter) in float64, 0 when the union is 0.  Until no pair with IoU >=
+ *   iou_threshold has both sides free: the pair of largest IoU, then smallest a position, then
+ *   smallest b position, is matched — the reference's stable descending sort and greedy sweep.
+ *   -> matched int32 [B][La] (b position or -1; -1 past the filtered length), b_match_count int32
+ *   [B][Lb] (0 past it), n_filtered int32 [B][2] (filtered lengths of a, b); all OVERWRITTEN.
+ *   A non-finite threshold: RGBD_E_ARG; na, nb, La or Lb > 256, or hw > 2^21: RGBD_E_SHAPE.
+ * rgbd_match_lut: lut int32 [B][na] (OVERWRITTEN) in the packing of rgbd_overlay_blend.
+ *   mode 0 ("gt", predictor.py:266-284): the listed, non-empty segment at list position i takes
+ *   gt_colors[b][id] (int32 [B][nb], r | g << 8 | b << 16, -1 = the mapping lacks the id) of the GT id
+ *   at filtered b position matched[b][i] when i < n_filtered[b][0] and matched[b][i] >= 0 — the
+ *   reference indexes the filtered arrays with the unfiltered position — and unmatched_color
+ *   (0..2^24-1) otherwise or where the mapping lacks the id; unlisted and empty ids get -1.
+ *   track and palette are not read.
+ *   mode 1 ("track"): lut[b][id] = palette[track[b][id] % n_colors] (palette uint8 [n_colors][3],
+ *   track int32 [B][na]) where track[b][id] >= 0, else -1; only track, palette, n_colors, lut, B
+ *   and na are read.  Another mode: RGBD_E_ARG.
+ * rgbd_track_assign: after a match with a_list = b_list = 0..Q-1 on counts [B][Q+1][Q+1] of this
+ *   frame's map against the previous frame's: track int32 [B][Q] (OVERWRITTEN) by segment id — a
+ *   matched segment takes prev_track[b][matched id], every other non-empty one next_track[b]++ in
+ *   ascending id order, empty ids -1.  next_track int32 [B] is updated in place.  Q > 256: RGBD_E_SHAPE.
+ * All: a NULL pointer or a non-positive size: RGBD_E_ARG, checked before any HIP call. */
+int rgbd_label_contingency(const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int na, int nb,
+                           int32_t* counts, void* stream);
+int rgbd_greedy_iou_match(const int32_t* counts, int B, int na, int nb, long long hw, const int32_t* a_list, int La,
+                          const int32_t* b_list, int Lb, double iou_threshold, int32_t* matched,
+                          int32_t* b_match_count, int32_t* n_filtered, void* stream);
+int rgbd_match_lut(int mode, const int32_t* counts, int B, int na, int nb, const int32_t* a_list, int La,
+                   const int32_t* b_list, int Lb, const int32_t* matched, const int32_t* n_filtered,
+                   const int32_t* gt_colors, int32_t unmatched_color, const int32_t* track, const uint8_t* palette,
+                   int n_colors, int32_t* lut, void* stream);
+int rgbd_track_assign(const int32_t* counts, int B, int Q, const int32_t* matched, const int32_t* prev_track,
+                      int32_t* next_track, int32_t* track, void* stream);
+
 /* ---------------------------------------------------------------- f4 segm mAP: mask IoU
  * The mask IoU of torchmetrics MeanAveragePrecision(iou_type="segm") as the reference's
  * Evaluator uses it (model_essential_part.py:56-157; pycocotools maskApi rleIou underneath).

@@ -15,7 +15,7 @@ LIB_PATH = Path(os.environ.get("RGBD_HIP_LIB", Path(__file__).resolve().parent /
 
 RGBD_F32 = 0
 RGBD_BF16 = 1
-RGBD_I32 = 2  # rgbd_overlay_blend: an int32 segment map
+RGBD_I32 = 2  # rgbd_overlay_blend, rgbd_label_contingency: an int32 segment map
 NBINS = 512
 
 # rgbd_decomp_info (include/rgbd_hip.h) as a numpy structured dtype: 2116 bytes, no padding
@@ -47,6 +47,10 @@ SIGNATURES = {
                               _P, _P, _P, _P, _P]),
     "rgbd_overlay_lut": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
     "rgbd_overlay_blend": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, ctypes.c_double, _P, _P]),
+    "rgbd_label_contingency": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "rgbd_greedy_iou_match": (_I, [_P, _I, _I, _I, _LL, _P, _I, _P, _I, ctypes.c_double, _P, _P, _P, _P]),
+    "rgbd_match_lut": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "rgbd_track_assign": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "rgbd_pack_mask_bits": (_I, [_P, _I, _LL, _P, _P, _P]),
     "rgbd_mask_intersections": (_I, [_P, _I, _P, _I, _LL, _P, _P]),
     "rgbd_resize_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),

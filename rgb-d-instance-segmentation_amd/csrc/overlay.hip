@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "label_cell.hpp"  // cell_id: the id a map cell names
 
 using namespace rgbd;
 
@@ -54,21 +55,6 @@ __global__ __launch_bounds__(OV_THR) void k_overlay_lut(const int* __restrict__ 
     v = (int32_t)p[0] | ((int32_t)p[1] << 8) | ((int32_t)p[2] << 16);
   }
   lut[(long long)b * n_ids + id] = v;
-}
-
-// the id a map cell names, or -1: float32 cells name an id only when they hold that integer exactly
-// (the reference compares the map with == against the integer id)
-template <bool F32>
-__device__ __forceinline__ int cell_id(uint32_t bits, int n_ids) {
-  if constexpr (F32) {
-    const float f = __uint_as_float(bits);
-    if (!(f >= 0.f && f < (float)n_ids)) return -1;  // NaN lands here too
-    const int i = (int)f;
-    return (float)i == f ? i : -1;
-  } else {
-    const int i = (int)bits;
-    return (i >= 0 && i < n_ids) ? i : -1;
-  }
 }
 
 __device__ __forceinline__ uint32_t blend_channel(uint32_t x, uint32_t c, float w0, double alpha) {

@@ -90,6 +90,8 @@ class StreamResult:
       overlay       uint8 [B,H,W,3]   the frame with every kept segment painted (None without ``overlay=``)
       seg_id, topk_idx  int32 [B,Q]   the tables of rgbd_pp_instance
       scores        float32 [B,Q]
+      track_id      int32 [B,Q]       by segment id: the track the segment belongs to, -1 for an id
+                                      without pixels (None without ``track=``)
 
     ``segments()`` is the only host wait."""
 
@@ -98,13 +100,15 @@ class StreamResult:
         self.segmentation = owner.segmentation
         self.overlay = owner.overlay_u8
         self.seg_id, self.topk_idx, self.scores = owner.seg_id, owner.topk_idx, owner.scores
+        self.track_id = owner.track_id
 
     def segments(self):
         """Wait for this call's replay, raise the reference's ValueError for a frame whose depth
         range the decomposition rejected, and return what
         ``postprocess.post_process_instance_segmentation(..., keep_on_device=True)`` returns: per
         image ``{"segmentation": float32 [H,W] on the device, "segments_info": [...]}``, read
-        from the pinned copy of the tables the replay made."""
+        from the pinned copy of the tables the replay made.  With ``track=`` every entry also
+        holds ``"track_id"``."""
         o = self._owner
         self._event.synchronize()
         for st in o._statuses:
@@ -112,10 +116,14 @@ class StreamResult:
         topk_h, sid_h = o._host[0].tolist(), o._host[1].tolist()
         ps_h = o._host[2].view(torch.float32).tolist()
         results = []
+        track_h = o._host[3].tolist() if o.track_cfg is not None else None
         for i in range(o.B):
             segments = [{"id": sid_h[i][j], "label_id": topk_h[i][j] % o.num_labels, "was_fused": False,
                          "score": round(ps_h[i][j], 6)}
                         for j in range(o.Q) if sid_h[i][j] >= 0]
+            if track_h is not None:
+                for seg in segments:
+                    seg["track_id"] = track_h[i][seg["id"]]
             results.append({"segmentation": o.segmentation[i], "segments_info": segments})
         return results
 
@@ -129,16 +137,27 @@ class StreamingSegmenter:
     there) -> the whole drop-in model in eval mode under no_grad (``set_compute_dtype(dtype,
     interface_dtype)``; bf16 runs under the bf16 autocast of the whole-model benchmark) ->
     ``rgbd_pp_instance`` at the frame's (H, W), the target size ``process_prediction`` asks for ->
-    with ``overlay=dict(alpha=0.6, palette=[(r, g, b), ...], color_by="label" | "id")`` the
+    with ``track=dict(iou_threshold=0.5)`` the tracking stage (below) -> with
+    ``overlay=dict(alpha=0.6, palette=[(r, g, b), ...], color_by="label" | "id" | "track")`` the
     colour table and the blend (csrc/overlay.hip) -> the copy of the tables to one pinned host
     block.  Between the frame copy and the event ``StreamResult.segments()`` waits on, nothing
     touches the host.
+
+    Segment ids are positions among the kept queries of one frame.  ``track=`` gives every segment
+    an id that is stable from frame to frame (csrc/segment_match.hip): the
+    contingency table of this frame's map against the previous frame's, the greedy IoU match of
+    the Q x Q segments, the assignment — a matched segment inherits its predecessor's track, the
+    other non-empty ones take fresh numbers in ascending id order — and the copy of map and track
+    table into the "previous" buffers, all in the captured path and on its stream.  The state
+    (previous map, its tracks, the next free number per image) lives on the device;
+    ``reset_tracks()`` forgets it.  ``overlay=dict(color_by="track")`` colours a segment by
+    ``palette[track % n_colors]``.  A track that is absent for a frame is not found again.
 
     ``model``: a CustomMask2FormerForUniversalSegmentation of version 0.4.0 on the GPU (put into
     eval mode here)."""
 
     def __init__(self, model, H, W, B=1, size=None, threshold=0.5, dtype=torch.bfloat16, interface_dtype=None,
-                 overlay=None):
+                 overlay=None, track=None):
         plm = model.model.pixel_level_module
         if getattr(plm, "version", None) != "0.4.0":
             raise ValueError("StreamingSegmenter runs the paper model (version 0.4.0), not "
@@ -158,10 +177,34 @@ class StreamingSegmenter:
         self.depth_u8 = torch.zeros((B, H, W), dtype=torch.uint8, device=dev)
         self.rgb_u8 = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=dev)
         self.segmentation = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        self._tables = torch.zeros((3, B, self.Q), dtype=torch.int32, device=dev)
+        self.track_cfg = None
+        if track is not None:
+            cfg = dict(iou_threshold=0.5)
+            unknown = set(track) - set(cfg)
+            if unknown:
+                raise ValueError(f"track: unknown keys {sorted(unknown)} (iou_threshold)")
+            cfg.update(track)
+            if self.Q > overlay_ops.MAX_MATCH_IDS or H * W > 1 << 21:
+                raise ValueError(f"track: at most {overlay_ops.MAX_MATCH_IDS} queries and 2^21 pixels per frame, got "
+                                 f"{self.Q} and {H * W}")
+            self.track_cfg = cfg
+        rows = 3 if self.track_cfg is None else 4  # the track table rides in the same pinned block
+        self._tables = torch.zeros((rows, B, self.Q), dtype=torch.int32, device=dev)
         self.topk_idx, self.seg_id = self._tables[0], self._tables[1]
         self.scores = self._tables[2].view(torch.float32)
-        self._host = torch.empty((3, B, self.Q), dtype=torch.int32, pin_memory=True)
+        self._host = torch.empty((rows, B, self.Q), dtype=torch.int32, pin_memory=True)
+        self.track_id = None
+        if self.track_cfg is not None:
+            Q = self.Q
+            self.track_id = self._tables[3]
+            self._prev_seg = torch.full((B, H, W), -1.0, dtype=torch.float32, device=dev)
+            self._prev_track = torch.full((B, Q), -1, dtype=torch.int32, device=dev)
+            self._next_track = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self._counts = torch.empty((B, Q + 1, Q + 1), dtype=torch.int32, device=dev)
+            self._ids = torch.arange(Q, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+            self._match = (torch.empty((B, Q), dtype=torch.int32, device=dev),
+                           torch.empty((B, Q), dtype=torch.int32, device=dev),
+                           torch.empty((B, 2), dtype=torch.int32, device=dev))
         self.overlay_cfg = None
         self.overlay_u8 = self._lut = self._palette = None
         if overlay is not None:
@@ -170,8 +213,10 @@ class StreamingSegmenter:
             if unknown:
                 raise ValueError(f"overlay: unknown keys {sorted(unknown)} (alpha, palette, color_by)")
             cfg.update(overlay)
-            if cfg["color_by"] not in ("label", "id"):
-                raise ValueError(f"overlay color_by {cfg['color_by']!r}: 'label' or 'id' expected")
+            if cfg["color_by"] not in ("label", "id", "track"):
+                raise ValueError(f"overlay color_by {cfg['color_by']!r}: 'label', 'id' or 'track' expected")
+            if cfg["color_by"] == "track" and self.track_cfg is None:
+                raise ValueError("overlay color_by 'track' needs track=dict(...)")
             if cfg["palette"] is None:
                 cfg["palette"] = overlay_ops.consistent_colors(max(self.num_labels, self.Q))
             self.overlay_cfg = cfg
@@ -202,9 +247,20 @@ class StreamingSegmenter:
         _lib.check(L.rgbd_pp_instance(ops._p(cls), ops._p(masks), B, Q, C1, masks.shape[-2], masks.shape[-1], self._th,
                                       self._tw, ctypes.c_double(self.threshold), self._seg_ptrs, ops._p(self.topk_idx),
                                       ops._p(self.scores), ops._p(self.seg_id), ops._p(ws), st), "rgbd_pp_instance")
-        if self.overlay_cfg is not None:
+        if self.track_cfg is not None:
+            overlay_ops.label_contingency(self.segmentation, self._prev_seg, Q, Q, out=self._counts)
+            overlay_ops.greedy_iou_match(self._counts, self._ids, self._ids, self.H * self.W,
+                                         self.track_cfg["iou_threshold"], out=self._match)
+            overlay_ops.track_assign(self._counts, self._match[0], self._prev_track, self._next_track,
+                                     out=self.track_id)
+            self._prev_seg.copy_(self.segmentation)
+            self._prev_track.copy_(self.track_id)
+        if self.overlay_cfg is not None and self.overlay_cfg["color_by"] == "track":
+            overlay_ops.track_lut(self.track_id, self._palette, out=self._lut)
+        elif self.overlay_cfg is not None:
             overlay_ops.build_lut(self.seg_id, self.topk_idx, self.num_labels, self._palette,
                                   self.overlay_cfg["color_by"], out=self._lut)
+        if self.overlay_cfg is not None:
             overlay_ops.blend(self.rgb_u8, self.segmentation, self._lut, self.overlay_cfg["alpha"], out=self.overlay_u8)
         self._host.copy_(self._tables, non_blocking=True)
 
@@ -228,7 +284,16 @@ class StreamingSegmenter:
             self._statuses = tuple(getattr(plm, "captured_statuses", ()))
             self.width = check_and_instantiate(graph, "StreamingSegmenter")
             self.graph = graph
+        self.reset_tracks()  # the warm-up runs tracked their own frames
         return self
+
+    def reset_tracks(self):
+        """Forget the previous frame: the next frame's segments get tracks 0, 1, ... in id order.
+        (Queued on the current stream, like the frame copies of a call.)"""
+        if self.track_cfg is not None:
+            self._prev_seg.fill_(-1.0)
+            self._prev_track.fill_(-1)
+            self._next_track.zero_()
 
     def __call__(self, depth_u8=None, rgb_u8=None):
         """Copy the frame (if given: uint8 [B,H,W] / [B,H,W,3], host or device) into the static

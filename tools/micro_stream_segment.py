@@ -4,6 +4,9 @@ round by round (the host is shared: a difference is trusted only against the spr
 
   replay  seg(depth, rgb) -> res.segments(): the host waits for the frame's event and reads the
           pinned tables; map and overlay stay on the device
+  replay_track  the same with track=dict(iou_threshold=0.5): contingency against the previous
+          frame, greedy match, track assignment and the two state copies inside the graph
+          (DESIGN §5.19); its cost per call is reported as the difference of the medians
   eager   data.map_10channel -> model -> postprocess.post_process_instance_segmentation (maps copied
           to the host, its default) -> the reference's overlay loop on the host in numpy
 
@@ -90,10 +93,17 @@ def main():
         seg = StreamingSegmenter(model, H, W, B=B, size=size, threshold=a.threshold, dtype=torch.bfloat16,
                                  overlay=dict(alpha=0.6, palette=palette, color_by="label")).capture()
 
+        seg_t = StreamingSegmenter(model, H, W, B=B, size=size, threshold=a.threshold, dtype=torch.bfloat16,
+                                   overlay=dict(alpha=0.6, palette=palette, color_by="label"),
+                                   track=dict(iou_threshold=0.5)).capture()
+
         host_s = [0.0]
 
         def replay(depth, rgb):
             return seg(depth, rgb).segments()
+
+        def replay_track(depth, rgb):
+            return seg_t(depth, rgb).segments()
 
         def eager(depth, rgb):
             model.set_compute_dtype(torch.bfloat16)
@@ -109,13 +119,13 @@ def main():
             return res, over
 
         kept = [len(r["segments_info"]) for r in replay(*batches[0])]
-        for fn in (replay, eager):  # warm both arms on every batch
+        for fn in (replay, replay_track, eager):  # warm every arm on every batch
             for bt in batches:
                 fn(*bt)
-        fps = {"replay": [], "eager": []}
+        fps = {"replay": [], "replay_track": [], "eager": []}
         host_s[0], t_eager = 0.0, 0.0
         for _ in range(a.rounds):
-            for arm, fn in (("replay", replay), ("eager", eager)):
+            for arm, fn in (("replay", replay), ("replay_track", replay_track), ("eager", eager)):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for i in range(a.frames):
@@ -132,8 +142,10 @@ def main():
                         "fps_max": round(max(v), 2)}
         rec["eager_host_overlay_share_of_time"] = round(host_s[0] / t_eager, 3)
         rec["replay_over_eager_median"] = round(rec["replay"]["fps_median"] / rec["eager"]["fps_median"], 3)
+        rec["track_ms_per_call_median"] = round(
+            1e3 * B * (1 / rec["replay_track"]["fps_median"] - 1 / rec["replay"]["fps_median"]), 3)
         _emit(rec, fh)
-        del seg
+        del seg, seg_t
         torch.cuda.empty_cache()
 
     H, W = 720, 1280
