@@ -1,7 +1,7 @@
 // Colour-map gradients of the fused hot path's end-to-end mode (rgbd_color_grads): up to four jobs
 //   out = G + D   (NCHW, in G's dtype; D absent: out = G + G)
 // in one launch, where D is the cascade gradient d cp1 as the DSAM dX legs leave it: NCHW (the
-// float32 mode) or NHWC (the bf16 modes).  The inverse of k_nchw_to_nhwc_multi (dsam_conv.hip)
+// float32 mode) or NHWC (the bf16 modes).  The inverse of k_nchw_to_nhwc_multi (layout.hip)
 // with an add on the way out: an NHWC source goes through a padded LDS tile, everything else is a
 // flat elementwise pass.  Each element is one float32 add and one rounding to G's dtype.
 // HBM-bound: reads G and D once, writes out once; no atomics, no workspace.

@@ -228,7 +228,7 @@ def test_dggm_cp1_nhwc_equals_nchw(shape):
 
 
 def _pack_reference(conv_w, proj_w, codes_present):
-    """numpy restatement of the bf16 code-merged packing (dsam_conv.hip, k_pack_codes):
+    """numpy restatement of the bf16 code-merged packing (dsam_pack.hip, k_pack_codes):
     W_k = proj + sum_{i in k} conv_i in f32 (proj first, conv_0..3 ascending), rounded once to bf16,
     laid out as wfwd [k][tap][Cin/32][Cout][32 c] / wbwd [k][tap][Cout/32][Cin][32 o] with the
     16-byte chunk g of row n at slot g ^ (((n >> 3) & 1) << 1)."""
