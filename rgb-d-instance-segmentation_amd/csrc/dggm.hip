@@ -1,15 +1,13 @@
-// K1 (DGGM-pre + 10-channel assembly) and K2 (DGGM gated fusion fwd/bwd) for gfx950.
-//
-// K1 follows calculate_gradient_features (reference mask2former/utils/data_process.py:1247-1305)
-// as called by map_10channel_case2 (mask2former/utils/dataloader.py:386-425).  The Sobel sums
-// of u8 depth are exact integers; sqrt and the normalising division use IEEE-rounded
-// intrinsics, so the planes are bit-exact to the numpy/OpenCV float32 result.
+// K2 (DGGM gated fusion fwd/bwd) for gfx950.
 //
 // K2 follows DepthGradientInjectionResidual.forward (custom_model.py:1204-1269) fused with the
 // final sum backbone_k = cp1_k + cp2_k (custom_model.py:355).  A workgroup computes the
 // resampled gate (3 bilinear taps x 4 + 1 nearest) of a pixel tile once into LDS and streams 32
 // channel planes of that tile with vector accesses (8 pixels per lane where h*w allows).
-#include <cstdlib>
+//
+// One kernel per direction (plus the backward's final reduction) serves up to four scales per
+// launch; the single-scale entry points launch it with one scale.
+#include <type_traits>
 
 #include "common.hpp"
 #include "timing.hpp"
@@ -18,217 +16,6 @@ using namespace rgbd;
 
 namespace {
 
-// image_mean / image_std of the reference's processor config
-// (mask2former/checkpoints/standard/preprocessor_config.json), rounded to float32 as
-// transformers' normalize does (np.array(mean, dtype=image.dtype)).  The config's std[1],
-// 0.2239999920129776, is one float32 ulp below 0.224f.
-__constant__ float kMean[3] = {0.48500001430511475f, 0.4560000002384186f, 0.4059999883174896f};
-__constant__ float kStd[3] = {0.2290000021457672f, 0.2239999920129776f, 0.22499999403953552f};
-constexpr double kRescale = 0.00392156862745098;  // rescale_factor of the same config
-
-struct PrepWs {
-  uint32_t min_bits;  // min over mag > 0 (non-negative floats order as their bits)
-  uint32_t max_bits;  // max over all mag
-};
-
-__global__ void k_prep_init(PrepWs* ws, int B) {
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) {
-    ws[b].min_bits = 0x7f800000u;
-    ws[b].max_bits = 0u;
-  }
-}
-
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  if (i < 0) return -i;
-  if (i >= n) return 2 * n - 2 - i;
-  return i;
-}
-
-__device__ __forceinline__ float norm_u8(uint8_t v, int c) {
-  // Mask2FormerImageProcessor (dataloader.py:405-410): transformers image_transforms.rescale
-  // multiplies in float64 and rounds once to float32; normalize is (x - mean_c) / std_c in
-  // float32, one rounding per op.
-  const float x = (float)__dmul_rn((double)v, kRescale);
-  return div_rn(__fsub_rn(x, kMean[c]), kStd[c]);
-}
-
-__global__ __launch_bounds__(256) void k_prep_pass1(const uint8_t* __restrict__ rgb,
-                                                    const uint8_t* __restrict__ depth, int H, int W,
-                                                    float* __restrict__ pv, PrepWs* ws) {
-  const int b = blockIdx.y;
-  const long long HW = (long long)H * W;
-  const uint8_t* d = depth + b * HW;
-  float* out = pv + b * 10 * HW;
-  float vmax = 0.f, vmin = __uint_as_float(0x7f800000u);
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < (int)HW; p += 256 * gridDim.x) {
-    const int y = p / W, x = p % W;
-    const uint8_t dv = d[p];
-    if (rgb) {
-      const uint8_t* px = rgb + (b * HW + p) * 3;
-      for (int c = 0; c < 3; ++c) out[c * HW + p] = norm_u8(px[c], c);
-    }
-    for (int c = 0; c < 3; ++c) out[(3 + c) * HW + p] = norm_u8(dv, c);
-    const int ym = reflect101(y - 1, H), yp = reflect101(y + 1, H);
-    const int xm = reflect101(x - 1, W), xp = reflect101(x + 1, W);
-    auto at = [&](int yy, int xx) { return (int)d[(long long)yy * W + xx]; };
-    const int gx = (at(ym, xp) - at(ym, xm)) + 2 * (at(y, xp) - at(y, xm)) + (at(yp, xp) - at(yp, xm));
-    const int gy = (at(yp, xm) - at(ym, xm)) + 2 * (at(yp, x) - at(ym, x)) + (at(yp, xp) - at(ym, xp));
-    float mag = sqrt_rn((float)(gx * gx + gy * gy));  // exact integer argument (< 2^24)
-    if (dv == 0) mag = 0.f;                               // invalid depth (:1265, :1278)
-    out[6 * HW + p] = mag;                                // scratch until pass 2
-    out[9 * HW + p] = mag > 0.f ? 1.f : 0.f;              // valid-gradient mask (:1282)
-    vmax = fmaxf(vmax, mag);
-    if (mag > 0.f) vmin = fminf(vmin, mag);
-  }
-  vmax = -wave_min(-vmax);
-  vmin = wave_min(vmin);
-  __shared__ float rmax[4], rmin[4];
-  if ((threadIdx.x & 63) == 0) {
-    rmax[threadIdx.x >> 6] = vmax;
-    rmin[threadIdx.x >> 6] = vmin;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // one atomic pair per block (same-address atomics serialise)
-    atomicMax(&ws[b].max_bits, __float_as_uint(fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]))));
-    atomicMin(&ws[b].min_bits, __float_as_uint(fminf(fminf(rmin[0], rmin[1]), fminf(rmin[2], rmin[3]))));
-  }
-}
-
-__global__ __launch_bounds__(256) void k_prep_pass2(int H, int W, float* __restrict__ pv,
-                                                    const PrepWs* ws) {
-  const int b = blockIdx.y;
-  const long long HW = (long long)H * W;
-  float* out = pv + b * 10 * HW;
-  const uint32_t mnb = ws[b].min_bits;
-  const float mn = __uint_as_float(mnb), mx = __uint_as_float(ws[b].max_bits);
-  const bool scale = (mnb != 0x7f800000u) && (mx > mn);  // :1285-1293
-  const float den = __fsub_rn(mx, mn);
-  for (long long p = blockIdx.x * 256ll + threadIdx.x; p < HW; p += 256ll * gridDim.x) {
-    const float mag = out[6 * HW + p];
-    const float v = scale ? div_rn(__fsub_rn(mag, mn), den) : 0.f;
-    out[6 * HW + p] = v;
-    out[7 * HW + p] = v;
-    out[8 * HW + p] = v;
-  }
-}
-
-// Quad variants (W % 4 == 0, every NYUv2 / RealSense width): a thread owns 4 x-consecutive
-// pixels — one 4-byte depth load per stencil row plus the two reflected edge bytes, three 4-byte
-// RGB loads, and one 16-byte store per output plane — instead of 9 byte loads and 8 scalar
-// stores per pixel.  Same arithmetic, same order per pixel, so the planes stay bit-exact.
-__device__ __forceinline__ void row6(const uint8_t* __restrict__ row, int x0, int W, int (&v)[6]) {
-  const uint32_t c = *reinterpret_cast<const uint32_t*>(row + x0);
-  v[0] = row[reflect101(x0 - 1, W)];
-  v[1] = c & 0xff;
-  v[2] = (c >> 8) & 0xff;
-  v[3] = (c >> 16) & 0xff;
-  v[4] = c >> 24;
-  v[5] = row[reflect101(x0 + 4, W)];
-}
-
-__global__ __launch_bounds__(256) void k_prep_pass1_q(const uint8_t* __restrict__ rgb,
-                                                      const uint8_t* __restrict__ depth, int H, int W,
-                                                      float* __restrict__ pv, float2* __restrict__ part) {
-  const int b = blockIdx.y;
-  const long long HW = (long long)H * W;
-  const int WQ = W >> 2;
-  const uint8_t* d = depth + b * HW;
-  float* out = pv + b * 10 * HW;
-  float vmax = 0.f, vmin = __uint_as_float(0x7f800000u);
-  const int nq = (int)(HW >> 2);
-  for (int q = blockIdx.x * 256 + threadIdx.x; q < nq; q += 256 * gridDim.x) {
-    const int y = q / WQ, x0 = (q - y * WQ) * 4;
-    const long long p = (long long)y * W + x0;
-    int up[6], mid[6], dn[6];
-    row6(d + (long long)reflect101(y - 1, H) * W, x0, W, up);
-    row6(d + (long long)y * W, x0, W, mid);
-    row6(d + (long long)reflect101(y + 1, H) * W, x0, W, dn);
-    if (rgb) {
-      const uint32_t* px = reinterpret_cast<const uint32_t*>(rgb + (b * HW + p) * 3);
-      const uint32_t w0 = px[0], w1 = px[1], w2 = px[2];
-      const uint8_t c[12] = {(uint8_t)w0, (uint8_t)(w0 >> 8), (uint8_t)(w0 >> 16), (uint8_t)(w0 >> 24),
-                             (uint8_t)w1, (uint8_t)(w1 >> 8), (uint8_t)(w1 >> 16), (uint8_t)(w1 >> 24),
-                             (uint8_t)w2, (uint8_t)(w2 >> 8), (uint8_t)(w2 >> 16), (uint8_t)(w2 >> 24)};
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch)
-        *reinterpret_cast<float4*>(out + ch * HW + p) =
-            make_float4(norm_u8(c[ch], ch), norm_u8(c[3 + ch], ch), norm_u8(c[6 + ch], ch), norm_u8(c[9 + ch], ch));
-    }
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-      *reinterpret_cast<float4*>(out + (3 + ch) * HW + p) =
-          make_float4(norm_u8(mid[1], ch), norm_u8(mid[2], ch), norm_u8(mid[3], ch), norm_u8(mid[4], ch));
-    float mag[4], msk[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int l = i, c = i + 1, r = i + 2;
-      const int gx = (up[r] - up[l]) + 2 * (mid[r] - mid[l]) + (dn[r] - dn[l]);
-      const int gy = (dn[l] - up[l]) + 2 * (dn[c] - up[c]) + (dn[r] - up[r]);
-      float m = sqrt_rn((float)(gx * gx + gy * gy));  // exact integer argument (< 2^24)
-      if (mid[c] == 0) m = 0.f;                         // invalid depth (:1265, :1278)
-      mag[i] = m;
-      msk[i] = m > 0.f ? 1.f : 0.f;                     // valid-gradient mask (:1282)
-      vmax = fmaxf(vmax, m);
-      if (m > 0.f) vmin = fminf(vmin, m);
-    }
-    *reinterpret_cast<float4*>(out + 6 * HW + p) = make_float4(mag[0], mag[1], mag[2], mag[3]);  // scratch
-    *reinterpret_cast<float4*>(out + 9 * HW + p) = make_float4(msk[0], msk[1], msk[2], msk[3]);
-  }
-  vmax = -wave_min(-vmax);
-  vmin = wave_min(vmin);
-  __shared__ float rmax[4], rmin[4];
-  if ((threadIdx.x & 63) == 0) {
-    rmax[threadIdx.x >> 6] = vmax;
-    rmin[threadIdx.x >> 6] = vmin;
-  }
-  __syncthreads();
-  // one (min, max) partial per block, reduced by pass 2 (no same-address atomics: 256 blocks of
-  // one image serialising on one L2 line cost ~25 us)
-  if (threadIdx.x == 0)
-    part[(long long)b * gridDim.x + blockIdx.x] =
-        make_float2(fminf(fminf(rmin[0], rmin[1]), fminf(rmin[2], rmin[3])),
-                    fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3])));
-}
-
-__global__ __launch_bounds__(256) void k_prep_pass2_q(int H, int W, float* __restrict__ pv,
-                                                      const float2* __restrict__ part, int nparts) {
-  const int b = blockIdx.y;
-  const long long HW = (long long)H * W;
-  float* out = pv + b * 10 * HW;
-  float lmn = __uint_as_float(0x7f800000u), lmx = 0.f;
-  for (int i = threadIdx.x; i < nparts; i += 256) {
-    const float2 v = part[(long long)b * nparts + i];
-    lmn = fminf(lmn, v.x);
-    lmx = fmaxf(lmx, v.y);
-  }
-  lmn = wave_min(lmn);
-  lmx = -wave_min(-lmx);
-  __shared__ float smn[4], smx[4];
-  if ((threadIdx.x & 63) == 0) {
-    smn[threadIdx.x >> 6] = lmn;
-    smx[threadIdx.x >> 6] = lmx;
-  }
-  __syncthreads();
-  const float mn = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
-  const float mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-  const uint32_t mnb = __float_as_uint(mn);
-  const bool scale = (mnb != 0x7f800000u) && (mx > mn);  // :1285-1293
-  const float den = __fsub_rn(mx, mn);
-  for (long long p = (blockIdx.x * 256ll + threadIdx.x) * 4; p < HW; p += 1024ll * gridDim.x) {
-    const float4 m = *reinterpret_cast<const float4*>(out + 6 * HW + p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (scale)
-      v = make_float4(div_rn(__fsub_rn(m.x, mn), den), div_rn(__fsub_rn(m.y, mn), den),
-                      div_rn(__fsub_rn(m.z, mn), den), div_rn(__fsub_rn(m.w, mn), den));
-    *reinterpret_cast<float4*>(out + 6 * HW + p) = v;
-    *reinterpret_cast<float4*>(out + 7 * HW + p) = v;
-    *reinterpret_cast<float4*>(out + 8 * HW + p) = v;
-  }
-}
-
-// ------------------------------------------------------------------ K2 fusion
 struct Gate {
   float g[3];
 };
@@ -379,8 +166,6 @@ __device__ __forceinline__ TileGates<PX> stage_gates(float (*sg)[512], float4* s
   return t;
 }
 
-// One (pixel tile bx, 32-channel block by) of the fused forward; the kernels below map block
-// indices onto it (one scale per launch, or all scales in one launch).
 // One pixel's 8 channels [c0, c0+8) of an NHWC map -> v[cc][j] (cc < 8); C % 8 == 0.
 template <typename T, int PX>
 __device__ __forceinline__ void load_nhwc8(const T* p, float (&v)[kWaveCh][PX], int j) {
@@ -399,6 +184,8 @@ __device__ __forceinline__ void load_nhwc8(const T* p, float (&v)[kWaveCh][PX], 
   }
 }
 
+// One (pixel tile bx, 32-channel block by) of the fused forward; the kernel below maps its flat
+// block index onto it.
 template <typename T, int PX, bool HAS1, bool CP1_NHWC = false>
 __device__ __forceinline__ void dggm_fwd_block(float (*sg)[512], float4* swb, int bx, int by,
                                                const T* __restrict__ cp1, const T* __restrict__ color,
@@ -445,19 +232,6 @@ __device__ __forceinline__ void dggm_fwd_block(float (*sg)[512], float4* swb, in
     for (int cc = 0; cc < kWaveCh; ++cc)
       if (cw + cc < C) PxN<T, PX>::store(out + ((long long)b * C + cw + cc) * hw + t.p, y[cc]);
   }
-}
-
-template <typename T, int PX, bool HAS1>
-__global__ __launch_bounds__(256) void k_dggm_fuse_fwd(const T* __restrict__ cp1, const T* __restrict__ color,
-                                                       const float* __restrict__ grad,
-                                                       const float* __restrict__ mask, long long pvs,
-                                                       int H, int W, int C, int h, int w,
-                                                       const float* __restrict__ wt,
-                                                       const float* __restrict__ bias, T* __restrict__ out) {
-  __shared__ float sg[3][512];
-  __shared__ float4 swb[kBlkCh];
-  dggm_fwd_block<T, PX, HAS1>(sg, swb, blockIdx.x, blockIdx.y, cp1, color, grad, mask, pvs, H, W, C, h, w, wt, bias,
-                              out);
 }
 
 // partial[tile][c][4] = sum over the tile's pixels of dout*relu'(pre) * (1, g0, g1, g2).  Each
@@ -525,44 +299,8 @@ __device__ __forceinline__ void dggm_bwd_block(float (*sg)[512], float4* swb, fl
   if (lane < 32 && c < C) partial[((long long)bx * C + c) * 4 + (idx & 3)] = s;
 }
 
-template <typename T, int PX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_dggm_fuse_bwd_partial(const T* __restrict__ dout,
-                                                               const float* __restrict__ grad,
-                                                               const float* __restrict__ mask,
-                                                               long long pvs, int H, int W, int C, int h,
-                                                               int w, const float* __restrict__ wt,
-                                                               const float* __restrict__ bias,
-                                                               float* __restrict__ partial) {
-  __shared__ float sg[3][512];
-  __shared__ float4 swb[kBlkCh];
-  __shared__ __attribute__((aligned(16))) float sred[4][64 * kRedStride];
-  dggm_bwd_block<T, PX>(sg, swb, sred, blockIdx.x, blockIdx.y, dout, grad, mask, pvs, H, W, C, h, w, wt, bias,
-                        partial);
-}
-
-__global__ __launch_bounds__(256) void k_dggm_fuse_bwd_final(const float* __restrict__ partial, int ntiles, int C,
-                                                              float* __restrict__ dw, float* __restrict__ db) {
-  // one block per (c, j); fixed-shape tree over the tiles: deterministic
-  __shared__ float red[256];
-  const int t = blockIdx.x;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < ntiles; i += 256) s += partial[(long long)i * C * 4 + t];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x) return;
-  const int c = t >> 2, j = t & 3;
-  if (j == 0)
-    db[c] = red[0];
-  else
-    dw[c * 3 + (j - 1)] = red[0];
-}
-
-// ---- all scales in one launch (the four backbone scales of one step): a flat block index is
-// mapped onto (scale, pixel tile, channel block); the vector width PX is per scale, uniform per
+// ---- up to four scales in one launch (the four backbone scales of one step): a flat block index
+// is mapped onto (scale, pixel tile, channel block); the vector width PX is per scale, uniform per
 // block.  Cuts three launch/drain tails per direction on the small scales.
 constexpr int DGGM_MAX_SCALES = 4;
 struct DggmScaleArgs {
@@ -590,6 +328,17 @@ __device__ __forceinline__ int dggm_scale_of(const DggmMulti& m, int blk) {
   return k;
 }
 
+// f(std::integral_constant<int, PX>) for the scale's vector width (8, 4 or 1)
+template <typename F>
+__device__ __forceinline__ void dggm_with_px(int px, F&& f) {
+  if (px == 8)
+    f(std::integral_constant<int, 8>{});
+  else if (px == 4)
+    f(std::integral_constant<int, 4>{});
+  else
+    f(std::integral_constant<int, 1>{});
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_dggm_fuse_fwd_multi(DggmMulti m, const float* __restrict__ grad,
                                                              const float* __restrict__ mask, long long pvs, int H,
@@ -600,37 +349,19 @@ __global__ __launch_bounds__(256) void k_dggm_fuse_fwd_multi(DggmMulti m, const 
   const DggmScaleArgs& d = m.s[k];
   const int local = blockIdx.x - d.blk0, bx = local % d.nbx, by = local / d.nbx;
   const T* cp1 = (const T*)d.cp1;
-  if (cp1 && d.cp1_nhwc) {
-    if (d.px == 8)
-      dggm_fwd_block<T, 8, true, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                       d.wt, d.bias, (T*)d.out);
-    else if (d.px == 4)
-      dggm_fwd_block<T, 4, true, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                       d.wt, d.bias, (T*)d.out);
-    else
-      dggm_fwd_block<T, 1, true, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                       d.wt, d.bias, (T*)d.out);
-  } else if (cp1) {
-    if (d.px == 8)
-      dggm_fwd_block<T, 8, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt,
-                                 d.bias, (T*)d.out);
-    else if (d.px == 4)
-      dggm_fwd_block<T, 4, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt,
-                                 d.bias, (T*)d.out);
-    else
-      dggm_fwd_block<T, 1, true>(sg, swb, bx, by, cp1, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt,
-                                 d.bias, (T*)d.out);
-  } else {
-    if (d.px == 8)
-      dggm_fwd_block<T, 8, false>(sg, swb, bx, by, nullptr, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                  d.wt, d.bias, (T*)d.out);
-    else if (d.px == 4)
-      dggm_fwd_block<T, 4, false>(sg, swb, bx, by, nullptr, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                  d.wt, d.bias, (T*)d.out);
-    else
-      dggm_fwd_block<T, 1, false>(sg, swb, bx, by, nullptr, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w,
-                                  d.wt, d.bias, (T*)d.out);
-  }
+  auto run = [&](auto has1, auto nhwc) __attribute__((always_inline)) {
+    dggm_with_px(d.px, [&](auto px) __attribute__((always_inline)) {
+      dggm_fwd_block<T, decltype(px)::value, decltype(has1)::value, decltype(nhwc)::value>(
+          sg, swb, bx, by, decltype(has1)::value ? cp1 : nullptr, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h,
+          d.w, d.wt, d.bias, (T*)d.out);
+    });
+  };
+  if (cp1 && d.cp1_nhwc)
+    run(std::true_type{}, std::true_type{});
+  else if (cp1)
+    run(std::true_type{}, std::false_type{});
+  else
+    run(std::false_type{}, std::false_type{});
 }
 
 template <typename T>
@@ -642,18 +373,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   const int k = dggm_scale_of(m, blockIdx.x);
   const DggmScaleArgs& d = m.s[k];
   const int local = blockIdx.x - d.blk0, bx = local % d.nbx, by = local / d.nbx;
-  if (d.px == 8)
-    dggm_bwd_block<T, 8>(sg, swb, sred, bx, by, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt, d.bias,
-                         d.partial);
-  else if (d.px == 4)
-    dggm_bwd_block<T, 4>(sg, swb, sred, bx, by, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt, d.bias,
-                         d.partial);
-  else
-    dggm_bwd_block<T, 1>(sg, swb, sred, bx, by, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h, d.w, d.wt, d.bias,
-                         d.partial);
+  dggm_with_px(d.px, [&](auto px) __attribute__((always_inline)) {
+    dggm_bwd_block<T, decltype(px)::value>(sg, swb, sred, bx, by, (const T*)d.color, grad, mask, pvs, H, W, d.C, d.h,
+                                           d.w, d.wt, d.bias, d.partial);
+  });
 }
 
-// the tile sums of every scale reduced in one launch: block = (scale, c, j), same fixed tree
+// the tile sums of every scale reduced in one launch: block = (scale, c, j); a fixed-shape tree
+// over the tiles: deterministic
 __global__ __launch_bounds__(256) void k_dggm_fuse_bwd_final_multi(DggmMulti m) {
   __shared__ float red[256];
   int k = 0, t = blockIdx.x;
@@ -678,151 +405,44 @@ __global__ __launch_bounds__(256) void k_dggm_fuse_bwd_final_multi(DggmMulti m) 
     d.dw[c * 3 + (j - 1)] = red[0];
 }
 
-
 int dggm_px(int h, int w) {
   const long long hw = (long long)h * w;
   return hw % 8 == 0 ? 8 : (hw % 4 == 0 ? 4 : 1);
 }
 
-template <typename T, int PX>
-void launch_fwd(const void* cp1, const void* color, const float* grad, const float* mask, long long pvs,
-                       int B, int H, int W, int C, int h, int w, const float* wt, const float* bias, void* out,
-                       hipStream_t s) {
-  dim3 grid(B * ceil_div((long long)h * w, 64 * PX), ceil_div(C, kBlkCh));
-  if (cp1)
-    k_dggm_fuse_fwd<T, PX, true><<<grid, 256, 0, s>>>((const T*)cp1, (const T*)color, grad, mask, pvs, H, W, C, h, w,
-                                                      wt, bias, (T*)out);
-  else
-    k_dggm_fuse_fwd<T, PX, false><<<grid, 256, 0, s>>>(nullptr, (const T*)color, grad, mask, pvs, H, W, C, h, w, wt,
-                                                       bias, (T*)out);
-}
+// pixel tiles of one scale over the batch (h * w < 2^31)
+long long dggm_tiles(int B, int h, int w) { return (long long)B * ceil_div((long long)h * w, 64 * dggm_px(h, w)); }
 
-template <typename T, int PX>
-void launch_bwd(const void* dout, const float* grad, const float* mask, long long pvs, int B, int H, int W,
-                       int C, int h, int w, const float* wt, const float* bias, float* partial, hipStream_t s) {
-  dim3 grid(B * ceil_div((long long)h * w, 64 * PX), ceil_div(C, kBlkCh));
-  k_dggm_fuse_bwd_partial<T, PX><<<grid, 256, 0, s>>>((const T*)dout, grad, mask, pvs, H, W, C, h, w, wt, bias,
-                                                       partial);
-}
-
-#define RGBD_DGGM_DISPATCH(FN, T, PX, ...) \
-  do {                                     \
-    if ((PX) == 8)                         \
-      FN<T, 8>(__VA_ARGS__);               \
-    else if ((PX) == 4)                    \
-      FN<T, 4>(__VA_ARGS__);               \
-    else                                   \
-      FN<T, 1>(__VA_ARGS__);               \
-  } while (0)
-
-}  // namespace
-
-extern "C" {
-
-constexpr int kPrepMaxParts = 1024;  // pass-1 blocks per image (quad path)
-size_t rgbd_assemble_workspace_size(int B) {
-  const size_t nb = (size_t)(B > 0 ? B : 1);
-  return align256(sizeof(PrepWs) * nb) + align256(sizeof(float2) * kPrepMaxParts * nb);
-}
-
-int rgbd_assemble_pixel_values(const uint8_t* rgb_u8, const uint8_t* depth_u8, int B, int H, int W,
-                               float* pv, void* ws, void* stream) {
-  RGBD_REQUIRE(depth_u8 && pv && ws, RGBD_E_ARG);
-  RGBD_REQUIRE(B > 0 && H > 0 && W > 0, RGBD_E_ARG);
-  hipStream_t s = (hipStream_t)stream;
-  PrepWs* w = (PrepWs*)ws;
-  TimerScope ts("assemble", s);
-  const long long HW = (long long)H * W;
-  RGBD_REQUIRE(HW < (1ll << 31), RGBD_E_SHAPE);
-  if (W % 4 == 0 && ((uintptr_t)pv & 15) == 0 && ((uintptr_t)depth_u8 & 3) == 0 && ((uintptr_t)rgb_u8 & 3) == 0) {
-    const int nparts = (int)std::min<long long>(std::min<long long>(ceil_div(HW / 4, 256), std::max(2048 / B, 16)),
-                                                kPrepMaxParts);
-    float2* part = (float2*)((char*)ws + align256(sizeof(PrepWs) * (size_t)B));
-    dim3 grid((unsigned)nparts, B);
-    k_prep_pass1_q<<<grid, 256, 0, s>>>(rgb_u8, depth_u8, H, W, pv, part);
-    k_prep_pass2_q<<<grid, 256, 0, s>>>(H, W, pv, part, nparts);
-  } else {
-    k_prep_init<<<ceil_div(B, 64), 64, 0, s>>>(w, B);
-    dim3 grid((unsigned)std::min<long long>(ceil_div(HW, 256), 128), B);
-    k_prep_pass1<<<grid, 256, 0, s>>>(rgb_u8, depth_u8, H, W, pv, w);
-    k_prep_pass2<<<grid, 256, 0, s>>>(H, W, pv, w);
-  }
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-int rgbd_dggm_fuse_fwd(int dtype, const void* cp1, const void* color, const float* grad,
-                       const float* mask, long long pv_batch_stride, int B, int H, int W, int C,
-                       int h, int w, const float* weight, const float* bias, void* out,
-                       void* stream) {
-  RGBD_REQUIRE(color && grad && mask && weight && bias && out, RGBD_E_ARG);
-  RGBD_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && h > 0 && w > 0, RGBD_E_ARG);
-  RGBD_REQUIRE((long long)h * w < (1ll << 31), RGBD_E_SHAPE);
-  hipStream_t s = (hipStream_t)stream;
-  TimerScope ts("dggm_fwd", s);
-  const int px = dggm_px(h, w);
-  if (dtype == RGBD_F32)
-    RGBD_DGGM_DISPATCH(launch_fwd, float, px, cp1, color, grad, mask, pv_batch_stride, B, H, W, C, h, w, weight,
-                       bias, out, s);
-  else if (dtype == RGBD_BF16)
-    RGBD_DGGM_DISPATCH(launch_fwd, bf16_t, px, cp1, color, grad, mask, pv_batch_stride, B, H, W, C, h, w, weight,
-                       bias, out, s);
-  else
-    return RGBD_E_DTYPE;
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-static int dggm_bwd_tiles(int B, int h, int w) { return B * ceil_div((long long)h * w, 64 * dggm_px(h, w)); }
-
-size_t rgbd_dggm_fuse_bwd_workspace_size(int B, int C, int h, int w) {
-  return align256(sizeof(float) * 4 * (size_t)C * dggm_bwd_tiles(B, h, w));
-}
-
-int rgbd_dggm_fuse_bwd(int dtype, const void* dout, const float* grad, const float* mask,
-                       long long pv_batch_stride, int B, int H, int W, int C, int h, int w,
-                       const float* weight, const float* bias, float* dweight, float* dbias,
-                       void* ws, void* stream) {
-  RGBD_REQUIRE(dout && grad && mask && weight && bias && dweight && dbias && ws, RGBD_E_ARG);
-  RGBD_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && h > 0 && w > 0, RGBD_E_ARG);
-  RGBD_REQUIRE((long long)h * w < (1ll << 31), RGBD_E_SHAPE);
-  hipStream_t s = (hipStream_t)stream;
-  TimerScope ts("dggm_bwd", s);
-  const int ntiles = dggm_bwd_tiles(B, h, w), px = dggm_px(h, w);
-  float* partial = (float*)ws;
-  if (dtype == RGBD_F32)
-    RGBD_DGGM_DISPATCH(launch_bwd, float, px, dout, grad, mask, pv_batch_stride, B, H, W, C, h, w, weight, bias,
-                       partial, s);
-  else if (dtype == RGBD_BF16)
-    RGBD_DGGM_DISPATCH(launch_bwd, bf16_t, px, dout, grad, mask, pv_batch_stride, B, H, W, C, h, w, weight, bias,
-                       partial, s);
-  else
-    return RGBD_E_DTYPE;
-  k_dggm_fuse_bwd_final<<<C * 4, 256, 0, s>>>(partial, ntiles, C, dweight, dbias);
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-
-// Multi-scale forms: scales given as host arrays (n <= 4), one launch (fwd) / two launches (bwd).
-static int dggm_multi_setup(int n, const int* C, const int* h, const int* w, int B, DggmMulti& m) {
+// The shapes, tile counts and block ranges of n scales (host arrays, n <= 4); the callers add the
+// pointers.  Slots and fields a call does not use stay zero.
+int dggm_multi_setup(int n, const int* C, const int* h, const int* w, int B, DggmMulti& m) {
   RGBD_REQUIRE(n >= 1 && n <= DGGM_MAX_SCALES && C && h && w, RGBD_E_ARG);
+  m = DggmMulti{};
   m.n = n;
-  int blk = 0;
+  long long blk = 0;
   for (int k = 0; k < n; ++k) {
     RGBD_REQUIRE(C[k] > 0 && h[k] > 0 && w[k] > 0 && (long long)h[k] * w[k] < (1ll << 31), RGBD_E_ARG);
+    const long long nbx = dggm_tiles(B, h[k], w[k]);
+    RGBD_REQUIRE(blk + nbx * ceil_div(C[k], kBlkCh) < (1ll << 31), RGBD_E_SHAPE);  // the flat grid
     DggmScaleArgs& d = m.s[k];
     d.C = C[k];
     d.h = h[k];
     d.w = w[k];
     d.px = dggm_px(h[k], w[k]);
-    d.nbx = B * ceil_div((long long)h[k] * w[k], 64 * d.px);
-    d.tiles = d.nbx;
-    d.blk0 = blk;
-    blk += d.nbx * ceil_div(C[k], kBlkCh);
+    d.nbx = d.tiles = (int)nbx;
+    d.blk0 = (int)blk;
+    blk += nbx * ceil_div(C[k], kBlkCh);
   }
-  m.total = blk;
+  m.total = (int)blk;
   return RGBD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rgbd_dggm_fuse_bwd_workspace_size(int B, int C, int h, int w) {
+  return align256(sizeof(float) * 4 * (size_t)C * (size_t)dggm_tiles(B, h, w));
 }
 
 size_t rgbd_dggm_fuse_bwd_multi_workspace_size(int n, const int* C_host, const int* h_host, const int* w_host,
@@ -832,6 +452,7 @@ size_t rgbd_dggm_fuse_bwd_multi_workspace_size(int n, const int* C_host, const i
   return tot;
 }
 
+// Scales given as host arrays (n <= 4): one launch.
 int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, int cp1_nhwc_mask,
                              const void* const* color_host, void* const* out_host, const float* const* weight_host,
                              const float* const* bias_host, const int* C_host, const int* h_host, const int* w_host,
@@ -851,8 +472,6 @@ int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, int 
     m.s[k].out = out_host[k];
     m.s[k].wt = weight_host[k];
     m.s[k].bias = bias_host[k];
-    m.s[k].partial = nullptr;
-    m.s[k].dw = m.s[k].db = nullptr;
   }
   hipStream_t s = (hipStream_t)stream;
   TimerScope ts("dggm_fwd", s);
@@ -866,6 +485,8 @@ int rgbd_dggm_fuse_fwd_multi(int dtype, int n, const void* const* cp1_host, int 
   return RGBD_OK;
 }
 
+// Two launches: the tile sums partial[tile][c][4] of every scale (scale k's at ws + the workspace
+// sizes of the scales before it), then their reduction.
 int rgbd_dggm_fuse_bwd_multi(int dtype, int n, const void* const* dout_host, const float* const* weight_host,
                              const float* const* bias_host, float* const* dweight_host, float* const* dbias_host,
                              const int* C_host, const int* h_host, const int* w_host, const float* grad,
@@ -881,9 +502,7 @@ int rgbd_dggm_fuse_bwd_multi(int dtype, int n, const void* const* dout_host, con
   int nfin = 0;
   for (int k = 0; k < n; ++k) {
     RGBD_REQUIRE(dout_host[k] && weight_host[k] && bias_host[k] && dweight_host[k] && dbias_host[k], RGBD_E_ARG);
-    m.s[k].cp1 = nullptr;
     m.s[k].color = dout_host[k];
-    m.s[k].out = nullptr;
     m.s[k].wt = weight_host[k];
     m.s[k].bias = bias_host[k];
     m.s[k].partial = (float*)p;
@@ -905,4 +524,29 @@ int rgbd_dggm_fuse_bwd_multi(int dtype, int n, const void* const* dout_host, con
   return RGBD_OK;
 }
 
+// The single-scale forms: their own argument checks and return codes, then the n = 1 case of the
+// calls above (the same kernels, tile decomposition, workspace layout and reduction tree).
+int rgbd_dggm_fuse_fwd(int dtype, const void* cp1, const void* color, const float* grad,
+                       const float* mask, long long pv_batch_stride, int B, int H, int W, int C,
+                       int h, int w, const float* weight, const float* bias, void* out,
+                       void* stream) {
+  RGBD_REQUIRE(color && grad && mask && weight && bias && out, RGBD_E_ARG);
+  RGBD_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && h > 0 && w > 0, RGBD_E_ARG);
+  RGBD_REQUIRE((long long)h * w < (1ll << 31), RGBD_E_SHAPE);
+  return rgbd_dggm_fuse_fwd_multi(dtype, 1, cp1 ? &cp1 : nullptr, 0, &color, &out, &weight, &bias, &C, &h, &w, grad,
+                                  mask, pv_batch_stride, B, H, W, stream);
+}
+
+int rgbd_dggm_fuse_bwd(int dtype, const void* dout, const float* grad, const float* mask,
+                       long long pv_batch_stride, int B, int H, int W, int C, int h, int w,
+                       const float* weight, const float* bias, float* dweight, float* dbias,
+                       void* ws, void* stream) {
+  RGBD_REQUIRE(dout && grad && mask && weight && bias && dweight && dbias && ws, RGBD_E_ARG);
+  RGBD_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && h > 0 && w > 0, RGBD_E_ARG);
+  RGBD_REQUIRE((long long)h * w < (1ll << 31), RGBD_E_SHAPE);
+  return rgbd_dggm_fuse_bwd_multi(dtype, 1, &dout, &weight, &bias, &dweight, &dbias, &C, &h, &w, grad, mask,
+                                  pv_batch_stride, B, H, W, ws, stream);
+}
+
 }  // extern "C"
+

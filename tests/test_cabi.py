@@ -35,6 +35,20 @@ def test_argument_validation_without_device():
     assert L.rgbd_nchw_to_nhwc(7, fake, fake, 1, 1, 1, 1, null) == -3
 
 
+def test_flat_grids_past_int_range_are_refused():
+    """The DGGM kernels and the NHWC multi kernel index one flat grid with an int: a call whose
+    block count, or a job whose H * W, does not fit is RGBD_E_SHAPE on the host, nothing launched."""
+    from rgbd_amd import ops
+    L = _lib.lib()
+    null, fake = ctypes.c_void_p(0), ctypes.c_void_p(0x1000)
+    # 65536 images x 2048 pixel tiles x 32 channel blocks = 2^32 blocks
+    assert L.rgbd_dggm_fuse_fwd(1, null, fake, fake, fake, 640, 65536, 8, 8, 1024, 1024, 1024, fake, fake, fake, null) == -2
+    assert L.rgbd_dggm_fuse_bwd(1, fake, fake, fake, 640, 65536, 8, 8, 1024, 1024, 1024, fake, fake, fake, fake, fake,
+                                null) == -2
+    job = (ops._NhwcJob * 1)(ops._NhwcJob(0x1000, 0x1000, 1, 8, 65536, 32768))
+    assert L.rgbd_nchw_to_nhwc_multi(1, job, null) == -2
+
+
 def test_dsam_run_calls_argument_validation_without_device():
     """The other K5 run calls, refused on the host like rgbd_dsam_fwd: null pointers RGBD_E_ARG and
     a contraction channel count that is no multiple of 8 RGBD_E_SHAPE with RGBD_F32 (dX contracts

@@ -151,11 +151,12 @@ def test_dsam_bf16_dx_nhwc_only_and_nhwc_bias_sums(k):
     torch.testing.assert_close(b[2], a[2], rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("shape", [(2, 96, 120, 160), (3, 40, 7, 8), (2, 768, 15, 20), (1, 12, 5, 5)])
+@pytest.mark.parametrize("shape", [(2, 96, 120, 160), (3, 40, 7, 8), (2, 768, 15, 20), (1, 12, 5, 5), (3, 72, 5, 8)])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_nchw_to_nhwc_exact(shape, dtype):
-    """rgbd_nchw_to_nhwc: the 16-byte bf16 path (h*w and C multiples of 8, ragged 64x64 tiles)
-    and the element-wise fallback are exact copies."""
+    """rgbd_nchw_to_nhwc: the 16-byte bf16 path (h*w and C multiples of 8, ragged 64x64 tiles;
+    3x72x5x8 has B > 1 with C and h*w multiples of 8 but not of 64: two channel tiles, one ragged
+    pixel tile per image) and the element-wise fallback are exact copies."""
     g = torch.Generator(device=DEV)
     g.manual_seed(11)
     x = torch.randn(shape, generator=g, device=DEV).to(dtype)

@@ -290,6 +290,26 @@ def test_nchw_to_nhwc_family(shape):
     assert torch.equal(ops.nchw_to_nhwc_multi([xb])[0], xb.permute(0, 2, 3, 1).contiguous())
 
 
+def test_dggm_single_forms_and_scalar_assemble():
+    """What the hot-path sweep does not call: the single-scale DGGM forms (one-scale launches of
+    the multi-scale kernels; the backward's workspace is exactly rgbd_dggm_fuse_bwd_workspace_size)
+    at h*w % 8 == 0, % 4 == 0 and odd, C ragged against the 32- and 8-channel blocks, and K1 alone
+    at W % 4 != 0 (the scalar path; its partials live in rgbd_assemble_workspace_size bytes)."""
+    from rgbd_amd import ops
+    g = torch.Generator().manual_seed(5)
+    depth = torch.randint(0, 256, (2, 9, 13), generator=g, dtype=torch.uint8).to(DEV)
+    rgb = torch.randint(0, 256, (2, 9, 13, 3), generator=g, dtype=torch.uint8).to(DEV)
+    _sweep(ops.assemble_pixel_values, depth, rgb)
+    pv = ops.assemble_pixel_values(depth, rgb)
+    for dt in (F32, BF16):
+        for C, h, w in [(40, 4, 6), (33, 3, 4), (8, 3, 5)]:
+            color, cp1, dout = (_randn(g, (2, C, h, w), dt) for _ in range(3))
+            wt, bs = _randn(g, (C, 3, 1, 1)), _randn(g, (C,))
+            _sweep(ops.dggm_fuse_fwd, cp1, color, pv, wt, bs)
+            _sweep(lambda c, p, w_, b_: ops.dggm_fuse_fwd(None, c, p, w_, b_), color, pv, wt, bs)
+            _sweep(ops.dggm_fuse_bwd, dout, pv, wt, bs)
+
+
 def test_dsam_legs_with_wrapper_made_plans():
     """bf16 DSAM legs called without ``plan=``: the wrapper plans the leg alone (ops.dsam_plan) and
     sizes the workspace for the run part only (rgbd_dsam_run_workspace_size).  97x131, B = 3

@@ -51,6 +51,28 @@ def test_assemble_degenerate_depth():
         np.testing.assert_array_equal(bits(pv[b, 6:]), bits(dggm_pre.dggm_planes(d[b])))
 
 
+@pytest.mark.parametrize("B,H,W,zero_image", [(2, 5, 7, False), (1, 3, 1, False), (2, 4, 6, True)],
+                         ids=["2x5x7", "1x3x1", "2x4x6_one_zero_image"])
+def test_assemble_scalar_path_bit_exact(B, H, W, zero_image):
+    """W % 4 != 0: the scalar pass 1 and the width-1 pass 2, which reduce the same per-block
+    (min, max) partials as the quad path.  3x1 has a one-pixel row (reflect101 with n == 1); the
+    all-zero image of 4x6 leaves its partials at (inf, 0): no valid gradient, planes 6:9 zero."""
+    ops = _ops()
+    rng = np.random.default_rng(100 * H + W)
+    depth = rng.integers(0, 256, (B, H, W), dtype=np.uint8)
+    depth[rng.random((B, H, W)) < 0.2] = 0  # invalid pixels
+    if zero_image:
+        depth[1] = 0
+    rgb = rng.integers(0, 256, (B, H, W, 3), dtype=np.uint8)
+    pv = ops.assemble_pixel_values(torch.from_numpy(depth).to(DEV), torch.from_numpy(rgb).to(DEV)).cpu().numpy()
+    for b in range(B):
+        ref = np.concatenate([synthetic.rgbd_planes({"rgb_u8": rgb[b], "depth_u8": depth[b]}),
+                              dggm_pre.dggm_planes(depth[b])])
+        np.testing.assert_array_equal(bits(pv[b]), bits(ref))
+    if zero_image:
+        assert not pv[1, 6:].any() and pv[0, 9].any()
+
+
 # ------------------------------------------------------------------ K3
 CASES = gi.decomposition_cases()
 
@@ -428,7 +450,10 @@ def test_graph_survives_a_larger_later_capture():
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_dggm_multi_scale_equals_per_scale(dtype):
     """rgbd_dggm_fuse_{fwd,bwd}_multi (all scales in one launch, as the fused hot path calls them)
-    give bitwise the per-scale entry points' outputs and gradients, incl. PX = 8 / 4 / 1 scales."""
+    give bitwise the per-scale entry points' outputs and gradients, incl. PX = 8 / 4 / 1 scales.
+    The per-scale entry points are n = 1 launches of the same kernels, so this checks the
+    multi-scale block indexing (scale lookup, block ranges, workspace offsets) against them; the
+    float64 evidence for n = 1 is test_gpu_dggm_ragged.py."""
     ops = _ops()
     B, H, W = 2, 97, 130
     pv = torch.from_numpy(gi.pixel_values(12, B, H, W)).to(DEV)
