@@ -770,6 +770,47 @@ int rgbd_match_lut(int mode, const int32_t* counts, int B, int na, int nb, const
 int rgbd_track_assign(const int32_t* counts, int B, int Q, const int32_t* matched, const int32_t* prev_track,
                       int32_t* next_track, int32_t* track, void* stream);
 
+/* ---------------------------------------------------------------- f7 compressed COCO RLE decoded on the device
+ * The reading half of the reference's per-image JSON (csrc/rle_decode.hip): pycocotools' maskApi.c
+ * rleFrString and rleDecode, and the composite of mask2former/predictor.py:974-1065
+ * (_load_json_prediction_data: painter's order, the empty-mask filter, the PIL NEAREST resize).
+ * Input, for N masks in B files: chars uint8 (device), the masks' count strings concatenated, and
+ * meta, int32 words given twice with the same contents — meta_host is validated before any
+ * launch, meta_dev is what the kernels read:
+ *   offsets [N+1]  character offsets, offsets[0] = 0, non-decreasing
+ *   hw [N][2]      each mask's own (h, w)
+ *   take [N]       0 | 1: 0 keeps a mask out of the map (the reference's "no label or score")
+ *   slot [N]       -1 where (h, w) equals the target, else k for the k-th mask whose size differs
+ *   resized [N]    resized[k] = the mask with slot k (entries past the last k are not read)
+ *   ranges [B+1]   file b holds masks ranges[b] .. ranges[b+1]-1; ranges[0] = 0, ranges[B] = N
+ * info int32 [N][4] (OVERWRITTEN): {number of counts, status, has a set pixel at the target size, 0};
+ *   status bits: 1 a negative count, 2 the counts do not sum to h w, 4 a truncated last group or a
+ *   count of more than 13 groups.  A mask with a non-zero status takes no part below.
+ * rgbd_rle_chunk: the characters one step of the counts stage takes (strings longer than it carry
+ *   from step to step).
+ * rgbd_rle_counts (maskApi.c rleFrString): ends uint32 [offsets[N]] (device): the inclusive run
+ *   end offsets E of mask m at ends[offsets[m] + i], i < number of counts; counts are E's differences.
+ * rgbd_rle_paint (predictor.py:1009-1053): out int32 [B][H][W] (OVERWRITTEN, 16-byte aligned): pixel
+ *   (y, x) of file b = i + 1 for the last mask i of the file (index within the file) with take = 1,
+ *   status 0 and a set pixel at the target size whose pixel (sy, sx) is set — the identity, or
+ *   Pillow's NEAREST source index where the mask's size differs from (H, W) — else 0.  No atomics:
+ *   bitwise repeatable.  ws: rgbd_rle_workspace_size(N, offsets[N], number of resized masks, H, W).
+ * rgbd_rle_stack (pycocotools.mask.decode, maskApi.c rleDecode): every mask of one size (h, w)
+ *   (B = 1 in meta), out uint8 [N][h][w] of 0 | 1 (OVERWRITTEN, 4-byte aligned); a mask with a
+ *   non-zero status is written as zeros.  ws as above with no resized mask.
+ * All: a NULL pointer, a non-positive size, offsets or ranges out of order, take outside 0 | 1,
+ *   slot / resized not as described, or (stack) a mask of another size: RGBD_E_ARG; H W or an h w
+ *   >= 2^31, B, N (stack) or the resized masks > 65535: RGBD_E_SHAPE; all checked on the host
+ *   before any HIP call.  The size query is pure (0 for a non-positive size). */
+int rgbd_rle_chunk(void);
+size_t rgbd_rle_workspace_size(int n_masks, long long n_chars, int n_resized, int H, int W);
+int rgbd_rle_counts(const uint8_t* chars, const int32_t* meta_host, const int32_t* meta_dev, int N, int B, int H,
+                    int W, uint32_t* ends, int32_t* info, void* stream);
+int rgbd_rle_paint(const uint8_t* chars, const int32_t* meta_host, const int32_t* meta_dev, int N, int B, int H, int W,
+                   int32_t* out, int32_t* info, void* ws, void* stream);
+int rgbd_rle_stack(const uint8_t* chars, const int32_t* meta_host, const int32_t* meta_dev, int N, int h, int w,
+                   uint8_t* out, int32_t* info, void* ws, void* stream);
+
 /* ---------------------------------------------------------------- f4 segm mAP: mask IoU
  * The mask IoU of torchmetrics MeanAveragePrecision(iou_type="segm") as the reference's
  * Evaluator uses it (model_essential_part.py:56-157; pycocotools maskApi rleIou underneath).

@@ -51,7 +51,12 @@ SIGNATURES = {
     "rgbd_greedy_iou_match": (_I, [_P, _I, _I, _I, _LL, _P, _I, _P, _I, ctypes.c_double, _P, _P, _P, _P]),
     "rgbd_match_lut": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
     "rgbd_track_assign": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
-    "rgbd_pack_mask_bits": (_I, [_P, _I, _LL, _P, _P, _P]),
+    "rgbd_rle_chunk": (_I, []),
+    "rgbd_rle_workspace_size": (_SZ, [_I, _LL, _I, _I, _I]),
+    "rgbd_rle_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "rgbd_rle_paint": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "rgbd_rle_stack": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "rgbd_pack_mask_bits":(_I, [_P, _I, _LL, _P, _P, _P]),
     "rgbd_mask_intersections": (_I, [_P, _I, _P, _I, _LL, _P, _P]),
     "rgbd_resize_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "rgbd_resize_pil_bilinear": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "pil_nearest.hpp"
 
 namespace rgbd {
 namespace {
@@ -111,15 +112,7 @@ __global__ __launch_bounds__(256) void k_pil_v(const uint8_t* __restrict__ src, 
 __global__ void k_pil_nearest_idx(int in_h, int out_h, int in_w, int out_w, int* __restrict__ iy, int* __restrict__ ix) {
   const int axis = threadIdx.x;
   if (axis > 1) return;
-  const int n_in = axis ? in_w : in_h, n_out = axis ? out_w : out_h;
-  int* idx = axis ? ix : iy;
-  const double a0 = (double)n_in / n_out;
-  double xx = 0.5 * a0;
-  for (int o = 0; o < n_out; ++o) {
-    int v = (int)xx;
-    idx[o] = v < 0 ? 0 : (v > n_in - 1 ? n_in - 1 : v);
-    xx += a0;
-  }
+  pil_nearest_walk(axis ? in_w : in_h, axis ? out_w : out_h, axis ? ix : iy);
 }
 
 __global__ __launch_bounds__(256) void k_pil_nearest(const uint8_t* __restrict__ src, int B, int H, int W, int C,
