@@ -190,7 +190,15 @@ __global__ __launch_bounds__(512) void k_rp_gate(const bf16_t* __restrict__ fus,
 // Pipeline: in step st waves 0-3 issue the weights of step st+1 (the next item's step 0 after
 // the last: a workgroup always owns the same channel half) before their MFMAs; waves 4-7 issue
 // a third of the next quarter's input (the next item's quarter 0 during quarter 3) after their
-// first 32 MFMAs; every wave waits for its own copies, then the step's one barrier.
+// first 32 MFMAs; every wave waits for its own copies, then the step's one barrier.  Every copy
+// is an LDS-DMA from a wave-uniform base (scalar registers) + a 32-bit lane offset; the tile
+// origins are computed once per item.
+// Fragments: per kx group a wave reads its 4 A fragments and B columns 0-3, then issues the
+// MFMAs column by column (nj outer, mi inner) and reads column nj + 4 into column nj's
+// registers right behind that column's MFMAs: 32 fragment registers, the second half of the B
+// reads under MFMAs.  Every A address of a step is one of eight per-lane bases + an immediate.
+// Reading the next group's or the next step's fragments ahead (a three-step weight ring for the
+// latter) measured no faster / slower: DESIGN 5.10.1.
 // MODE 0 (train): y stored fragment-native per item [item = 2 tile + half][wave][mi][np][lane][8]
 //   (1 KiB contiguous per store instruction) and the BN statistics of the float32 conv outputs
 //   kept in registers across items -> slab[256][workgroup][2] (the other half's entries zero).
@@ -218,6 +226,16 @@ constexpr int C4_AK = (C4_APIECES + 3) / 4;  // input pieces per copying wave an
 static_assert(2 * C4_A_BYTES >= 8 * 128 * 2 * 4, "conv5 v4 statistics scratch");
 
 __device__ __forceinline__ uint32_t c4_off(int row, int chunk) { return row * 64 + 16 * (chunk ^ ((row >> 1) & 2)); }
+
+// LDS-DMA of 16 bytes per lane from a wave-uniform base + a 32-bit per-lane offset (no 64-bit
+// per-lane address arithmetic, no address register pair per piece)
+__device__ __forceinline__ void c4_dma(const void* sbase, uint32_t voff, uint32_t lds_base) {
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(sbase), "s"(lds_base)
+               : "memory");
+}
 
 struct C4Tile {
   int b, y0, x0;
@@ -303,15 +321,16 @@ __global__ __launch_bounds__(512) void k_rp_conv5_v4(const bf16_t* __restrict__ 
     const int hy = row / C4_PW, hx = row - hy * C4_PW;
     aoff[k] = row < C4_NPIX ? (uint32_t)((hy * PW + hx) * 64 + 16 * (q ^ ((row >> 1) & 2))) : 0u;
   }
-  auto issue_a = [&](const C4Tile& t, int qt, int sl, int k) {
-    const char* base = (const char*)(x + ((long long)t.b * 4 + qt) * plane + ((long long)t.y0 * PW + t.x0) * 32);
-    dma_lds16(base + aoff[k], lds0 + sl * C4_A_BYTES + ((wave & 3) + 4 * k) * 1024);
+  // xt: the tile's padded origin in quarter plane 0 of its image
+  auto issue_a = [&](const bf16_t* xt, int qt, int sl, int k) {
+    c4_dma(xt + qt * plane, aoff[k], lds0 + sl * C4_A_BYTES + ((wave & 3) + 4 * k) * 1024);
   };
+  auto tile_origin = [&](const C4Tile& t) { return x + (long long)t.b * 4 * plane + ((long long)t.y0 * PW + t.x0) * 32; };
   // weight pieces k0..k1-1 (of 24) of step st into buffer st & 1
   auto issue_b = [&](int st, int k0, int k1) {
-    const char* src = w5q + (size_t)st * C4_B_BYTES + 16 * lane;
+    const char* src = w5q + (size_t)st * C4_B_BYTES;
     const uint32_t dst = lds0 + C4_B_OFF + (st & 1) * C4_B_BYTES;
-    for (int k = k0; k < k1; ++k) dma_lds16(src + 1024 * k, dst + 1024 * k);
+    for (int k = k0; k < k1; ++k) c4_dma(src + 1024 * k, 16 * lane, dst + 1024 * k);
   };
   const bool loader = wave < 4;
 
@@ -331,13 +350,30 @@ __global__ __launch_bounds__(512) void k_rp_conv5_v4(const bf16_t* __restrict__ 
     if (!loader) {
 #pragma unroll
       for (int k = 0; k < C4_AK; ++k)
-        if ((wave & 3) + 4 * k < C4_APIECES) issue_a(t, 0, 0, k);
+        if ((wave & 3) + 4 * k < C4_APIECES) issue_a(tile_origin(t), 0, 0, k);
     }
     issue_b(0, 3 * wave, 3 * wave + 3);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-
+  // Fragment addresses.  A row mi of tap (ky, kx) is halo pixel p = P + c, P = 68 wave + r + C4_PW ky
+  // per lane and step, c = (mi >> 1) * C4_PW + (mi & 1) * 16 + kx a constant; c4_off(p, g) = 64 p +
+  // (16 g ^ 32 bit2(p)) and bit2(P + c) = bit2(P + (c & 7)), so eight per-lane bases xa[c & 7],
+  // computed at the step top, and the constant 64 c as the read's immediate offset give every
+  // address of the step.
+  // B column nj of tap kx is row 128 kx + 16 nj + r, whose swizzle depends on r alone: one base.
+  uint32_t xa[8];
+  const uint32_t xb = C4_B_OFF + c4_off(r, g);
+  auto rd_a = [&](int kx, int mi) {
+    if constexpr (C4_NODMA & 8) return make_uint4(lane, kx, 0, mi);
+    const int c = (mi >> 1) * C4_PW + (mi & 1) * 16 + kx;
+    return *reinterpret_cast<const uint4*>(smem + xa[c & 7] + 64 * c);
+  };
+  auto rd_b = [&](uint32_t bo, int kx, int nj) {  // bo = xb + the weight buffer's offset
+    if constexpr (C4_NODMA & 8) return make_uint4(nj, lane, kx, 0);
+    return *reinterpret_cast<const uint4*>(smem + bo + (kx * 128 + 16 * nj) * 64);
+  };
+  Frag<bf16_t> fa[4], fb[4];
 #ifdef C4_STAMPS
   int tcount = 0;
 #endif
@@ -349,6 +385,9 @@ __global__ __launch_bounds__(512) void k_rp_conv5_v4(const bf16_t* __restrict__ 
     const long long ntile = tile + npairs;
     const bool has_next = ntile < ntiles;
     const C4Tile tn = c4_tile(has_next ? ntile : tile, tiles_x, tiles_y);
+    // the origins of this tile and the next one, once per item (selecting between the tiles at
+    // each copy repeated the tile decomposition's divisions there)
+    const bf16_t *xt = tile_origin(t), *xn = tile_origin(tn);
     f32x4 acc[4][8];
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
@@ -358,40 +397,39 @@ __global__ __launch_bounds__(512) void k_rp_conv5_v4(const bf16_t* __restrict__ 
 #pragma unroll 1
     for (int st = 0; st < C4_STEPS; ++st) {
       const int qt = st / 3, ky = st - 3 * qt;
+      const int qn = qt + 1;  // the quarter copied during this one (4: the next item's quarter 0)
+      const bool a_go = !(C4_NODMA & 2) && !loader && (qn < 4 || has_next);
       C4_STAMP(0);
       if (!(C4_NODMA & 1) && loader && (st + 1 < C4_STEPS || has_next))
         issue_b(st + 1 < C4_STEPS ? st + 1 : 0, 6 * wave, 6 * wave + 6);
       C4_STAMP(1);
-      const int qn = qt + 1;  // the quarter copied during this one (4: the next item's quarter 0)
-      const bool a_go = !(C4_NODMA & 2) && !loader && (qn < 4 || has_next);
-      const char* sa = smem + (qt & 1) * C4_A_BYTES;
-      const char* sb = smem + C4_B_OFF + (st & 1) * C4_B_BYTES;
+      const uint32_t sb = xb + (st & 1) * C4_B_BYTES;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        xa[k] = (qt & 1) * C4_A_BYTES + c4_off(68 * wave + r + C4_PW * ky + k, g) - 64 * k;
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        Frag<bf16_t> fa[4], fb[8];
-        if constexpr (!(C4_NODMA & 8)) {
+        // The group's 4 A fragments and its first 4 B fragments; column nj's B registers take
+        // column nj + 4 as soon as its four MFMAs are issued, so the second half of the B reads
+        // runs under MFMAs.  Each accumulator gets one MFMA per group: the order inside a group
+        // is free, the K order (quarter, ky, kx) of every accumulator is unchanged.
 #pragma unroll
-          for (int mi = 0; mi < 4; ++mi) {
-            const int p = (2 * wave + (mi >> 1) + ky) * C4_PW + (mi & 1) * 16 + r + kx;
-            fa[mi].v = *reinterpret_cast<const uint4*>(sa + c4_off(p, g));
-          }
+        for (int mi = 0; mi < 4; ++mi) fa[mi].v = rd_a(kx, mi);
 #pragma unroll
-          for (int nj = 0; nj < 8; ++nj) fb[nj].v = *reinterpret_cast<const uint4*>(sb + c4_off(kx * 128 + 16 * nj + r, g));
-        } else {
+        for (int nj = 0; nj < 4; ++nj) fb[nj].v = rd_b(sb, kx, nj);
 #pragma unroll
-          for (int mi = 0; mi < 4; ++mi) fa[mi].v = make_uint4(lane, kx, st, mi);
+        for (int nj = 0; nj < 8; ++nj) {
 #pragma unroll
-          for (int nj = 0; nj < 8; ++nj) fb[nj].v = make_uint4(nj, lane, kx, st);
+          for (int mi = 0; mi < 4; ++mi) mma(acc[mi][nj], fa[mi], fb[nj & 3]);
+          __builtin_amdgcn_sched_barrier(0);  // the read stays between this column's MFMAs and the next one's
+          if (nj < 4) fb[nj].v = rd_b(sb, kx, nj + 4);
+          __builtin_amdgcn_sched_barrier(0);
         }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int nj = 0; nj < 8; ++nj) mma(acc[mi][nj], fa[mi], fb[nj]);
         if (kx == 0 && a_go) {  // this step's 13 pieces [13 ky, 13 ky + 13) of the next quarter
 #pragma unroll
           for (int k = 0; k < C4_AK; ++k) {
             const int j = (wave & 3) + 4 * k;
-            if (j >= 13 * ky && j < 13 * ky + 13 && j < C4_APIECES) issue_a(qn < 4 ? t : tn, qn & 3, qn & 1, k);
+            if (j >= 13 * ky && j < 13 * ky + 13 && j < C4_APIECES) issue_a(qn < 4 ? xt : xn, qn & 3, qn & 1, k);
           }
         }
         if (kx == 0) C4_STAMP(2);

@@ -25,6 +25,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("others", nargs="+")
 ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--per-round", action="store_true", help="also print every round's per-kernel averages (noise estimate)")
 ap.add_argument("--bytes", action="store_true",
                 help="no timing: rgbd_ratio_forward of every build on the same packed weights, small shapes, both "
                      "dtypes, train and eval; ratio, workspace and BN running statistics compared bytewise")
@@ -128,5 +129,9 @@ for tag, L in libs.items():
     outs[tag] = m(d).cpu()
 _lib._lib = new
 m.train()
+if a.per_round:
+    for tag in libs:
+        for n in names + ["total"]:
+            print(tag, n, "rounds:", " ".join(f"{v:.4f}" for v in res[tag][n]))
 for tag in libs:
     print(tag, "ratio==new:", bool(torch.equal(outs[tag], outs["new"])), "  ".join(f"{n} {statistics.median(v):.4f} ms (min {min(v):.4f})" for n, v in res[tag].items()))
