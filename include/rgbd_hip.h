@@ -811,6 +811,47 @@ int rgbd_rle_paint(const uint8_t* chars, const int32_t* meta_host, const int32_t
 int rgbd_rle_stack(const uint8_t* chars, const int32_t* meta_host, const int32_t* meta_dev, int N, int h, int w,
                    uint8_t* out, int32_t* info, void* ws, void* stream);
 
+/* ---------------------------------------------------------------- f4 compressed COCO RLE encoded on the device
+ * The writing half of the reference's per-image JSON (csrc/rle_encode.hip):
+ * pycocotools.mask.encode (maskApi.c rleEncode + rleToString) with the box of
+ * _calculate_bbox_from_mask (mask2former/predictor.py:460-490) and the area, for the masks of
+ * _convert_single_prediction_to_json (:376-457) and _convert_single_gt_label_to_json (:528-625).
+ * Integer-only, one writer per output word and byte: bitwise repeatable.  mode: 0 label maps, 1 a stack.
+ * rgbd_rle_encode_labels (replaces `segmentation == id` per segment + encode): maps [B][H][W] of
+ *   dtype RGBD_F32 | RGBD_I32 (device); a cell names id i in [0, n_ids) when it holds that integer
+ *   exactly (NaN, fractions and other values name none).  ids int32 [B][Q] (device): mask b Q + j
+ *   is `cell == ids[b][j]` of map b; a negative id marks an unused slot (0 counts, 0 characters,
+ *   area 0); duplicates, and ids no cell holds (one count, h w), are allowed.  N = B Q.
+ * rgbd_rle_encode_stack (replaces pycocotools.mask.encode of N masks): masks uint8 [N][h][w]
+ *   (device), set where non-zero.
+ * Output (device, OVERWRITTEN): chars uint8 [cap_chars], the strings concatenated; offsets int32
+ *   [N+1], mask m's string at chars[offsets[m] .. offsets[m+1]) — what rgbd_rle_counts /
+ *   rgbd_rle_stack take; info int32 [N][8] = {number of counts, number of characters the mask
+ *   needs, area, x0, y0, x1, y1 (inclusive; 0, 0, -1, -1 for an empty mask), status}; totals
+ *   int64 [2] = {counts needed by all masks, characters needed by the masks whose counts fit}.
+ *   Nothing is written past cap_counts run ends or min(cap_chars, 2^31 - 1) characters: status
+ *   bit 1 = the mask's counts did not fit (its characters are then unknown and not in totals[1]),
+ *   bit 2 = its characters did not fit; either way it gets no characters (offsets[m+1] = offsets[m]).
+ * rgbd_rle_encode_capacity: counts / chars that no call of that shape exceeds (0 / 0 for a
+ *   non-positive size): stack n_masks (h w + 1); label maps n_images 2 (H W - 1) + 2 n_masks for
+ *   ids that are distinct within an image (each duplicate slot can add up to H W + 1 more); chars =
+ *   counts times the characters of a count of H W cells.  RGBD_E_ARG for another mode or a NULL.
+ * rgbd_rle_encode_workspace_size: ws bytes for (mode, n_images, n_masks, H, W, cap_counts) (stack:
+ *   n_images is not used beyond its sign); pure, 0 for a non-positive size or a negative capacity.
+ * rgbd_rle_encode_chunk: the cells one workgroup step takes.
+ * Both encoders: a NULL or misaligned pointer (ws 16 bytes, totals 8), a non-positive size, a negative
+ *   capacity, n_ids outside 1..256: RGBD_E_ARG; a dtype other than the two: RGBD_E_DTYPE; H W >= 2^31,
+ *   B Q or N > 65535: RGBD_E_SHAPE; all checked on the host before any HIP call.  No host wait:
+ *   capturable. */
+int rgbd_rle_encode_chunk(void);
+int rgbd_rle_encode_capacity(int mode, int n_images, int n_masks, int H, int W, long long* counts, long long* chars);
+size_t rgbd_rle_encode_workspace_size(int mode, int n_images, int n_masks, int H, int W, long long cap_counts);
+int rgbd_rle_encode_labels(int dtype, const void* maps, int B, int H, int W, int n_ids, const int32_t* ids, int Q,
+                           long long cap_counts, long long cap_chars, uint8_t* chars, int32_t* offsets, int32_t* info,
+                           long long* totals, void* ws, void* stream);
+int rgbd_rle_encode_stack(const uint8_t* masks, int N, int h, int w, long long cap_counts, long long cap_chars,
+                          uint8_t* chars, int32_t* offsets, int32_t* info, long long* totals, void* ws, void* stream);
+
 /* ---------------------------------------------------------------- f4 segm mAP: mask IoU
  * The mask IoU of torchmetrics MeanAveragePrecision(iou_type="segm") as the reference's
  * Evaluator uses it (model_essential_part.py:56-157; pycocotools maskApi rleIou underneath).

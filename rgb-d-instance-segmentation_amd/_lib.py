@@ -56,6 +56,11 @@ SIGNATURES = {
     "rgbd_rle_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "rgbd_rle_paint": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rgbd_rle_stack": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "rgbd_rle_encode_chunk": (_I, []),
+    "rgbd_rle_encode_capacity": (_I, [_I, _I, _I, _I, _I, _P, _P]),
+    "rgbd_rle_encode_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _LL]),
+    "rgbd_rle_encode_labels": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _LL, _LL, _P, _P, _P, _P, _P, _P]),
+    "rgbd_rle_encode_stack": (_I, [_P, _I, _I, _I, _LL, _LL, _P, _P, _P, _P, _P, _P]),
     "rgbd_pack_mask_bits":(_I, [_P, _I, _LL, _P, _P, _P]),
     "rgbd_mask_intersections": (_I, [_P, _I, _P, _I, _LL, _P, _P]),
     "rgbd_resize_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),

@@ -15,12 +15,15 @@ outside the hot path).
 """
 import contextlib
 import ctypes
+import logging
 
 import torch
 
-from . import _lib, data, ops, overlay as overlay_ops
+from . import _lib, data, export, ops, overlay as overlay_ops
 from .graph_guard import check_and_instantiate
 from .hot_path import hot_path, prepare
+
+export_log = logging.getLogger(export.__name__)  # to_json warns where prediction_to_json warns
 
 
 class StreamingHotPath:
@@ -93,7 +96,7 @@ class StreamResult:
       track_id      int32 [B,Q]       by segment id: the track the segment belongs to, -1 for an id
                                       without pixels (None without ``track=``)
 
-    ``segments()`` is the only host wait."""
+    ``segments()`` is the only host wait (``to_json()``, with ``encode=True``, waits on the same event)."""
 
     def __init__(self, owner, event):
         self._owner, self._event = owner, event
@@ -127,6 +130,46 @@ class StreamResult:
             results.append({"segmentation": o.segmentation[i], "segments_info": segments})
         return results
 
+    def to_json(self, original_size=None):
+        """Per image exactly what ``export.prediction_to_json(self.segments()[i], original_size)``
+        returns — ``{"labels", "scores", "bboxes", "masks"}``, and with ``track=`` a ``"track_ids"``
+        list alongside ``labels`` — from the strings, boxes and areas the replay itself encoded
+        (``StreamingSegmenter(encode=True)``; csrc/rle_encode.hip).  Waits on the event
+        ``segments()`` waits on, reads the per-mask block from its pinned copy and then exactly the
+        characters.  ``original_size``: one (h, w) written as every mask's ``size``."""
+        o = self._owner
+        if o._enc is None:
+            raise RuntimeError("to_json needs StreamingSegmenter(encode=True)")
+        results = self.segments()
+        head = o._enc["host"].numpy()
+        N = o.B * o.Q
+        offsets, info = head[4:5 + N], head[5 + N:].reshape(N, 8)
+        if info[:, 7].any():  # the buffers hold the bound no frame exceeds
+            raise RuntimeError(f"StreamingSegmenter: the encoder's buffers overflowed (status {info[:, 7].max()})")
+        text = o._enc["chars"][:int(offsets[-1])].cpu().numpy().tobytes().decode("ascii")
+        h, w = (int(original_size[0]), int(original_size[1])) if original_size is not None else (o.H, o.W)
+        sid_h = o._host[1].tolist()
+        out = []
+        for i, res in enumerate(results):
+            slot = {sid: j for j, sid in enumerate(sid_h[i]) if sid >= 0}
+            data = {"labels": [], "scores": [], "bboxes": [], "masks": []}
+            if o.track_cfg is not None:
+                data["track_ids"] = []
+            for s in res["segments_info"]:
+                m = i * o.Q + slot[s["id"]]
+                _, _, area, x0, y0, x1, y1, _ = (int(v) for v in info[m])
+                if area == 0:
+                    export_log.warning("instance id %s has an empty mask: skipped", s["id"])
+                    continue
+                data["labels"].append(int(s["label_id"]))
+                data["scores"].append(float(s.get("score", 1.0)))
+                data["bboxes"].append([float(x0), float(y0), float(x1 - x0 + 1), float(y1 - y0 + 1)])
+                data["masks"].append({"size": [h, w], "counts": text[offsets[m]:offsets[m + 1]]})
+                if o.track_cfg is not None:
+                    data["track_ids"].append(s["track_id"])
+            out.append(data)
+        return out
+
 
 class StreamingSegmenter:
     """C5 end to end: u8 frames in, instance map, segment tables and blended overlay out, one
@@ -153,11 +196,18 @@ class StreamingSegmenter:
     ``reset_tracks()`` forgets it.  ``overlay=dict(color_by="track")`` colours a segment by
     ``palette[track % n_colors]``.  A track that is absent for a frame is not found again.
 
+    ``encode=True`` records the stream: ``rgbd_rle_encode_labels`` (csrc/rle_encode.hip, DESIGN.md
+    §5.21) runs in the captured path after ``rgbd_pp_instance`` (and the tracking stage) on the
+    float32 map with the device ``seg_id`` table as its ids, into static buffers sized by
+    ``rgbd_rle_encode_capacity`` — the bound no frame exceeds — and its per-mask block rides to a
+    pinned block of its own beside the tables; ``StreamResult.to_json()`` returns the reference's
+    per-image JSON from them.  Without it nothing of this exists: no buffer, no launch.
+
     ``model``: a CustomMask2FormerForUniversalSegmentation of version 0.4.0 on the GPU (put into
     eval mode here)."""
 
     def __init__(self, model, H, W, B=1, size=None, threshold=0.5, dtype=torch.bfloat16, interface_dtype=None,
-                 overlay=None, track=None):
+                 overlay=None, track=None, encode=False):
         plm = model.model.pixel_level_module
         if getattr(plm, "version", None) != "0.4.0":
             raise ValueError("StreamingSegmenter runs the paper model (version 0.4.0), not "
@@ -223,6 +273,20 @@ class StreamingSegmenter:
             self._palette = overlay_ops._palette(cfg["palette"], dev)
             self._lut = torch.empty((B, self.Q), dtype=torch.int32, device=dev)
             self.overlay_u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        self._enc = None
+        if encode:
+            N = B * self.Q
+            if self.Q > export.MAX_IDS or N > export.MAX_DEVICE_MASKS or H * W >= 2 ** 31:
+                raise ValueError(f"encode: at most {export.MAX_IDS} queries, {export.MAX_DEVICE_MASKS} masks and 2^31 - 1 "
+                                 f"pixels per frame, got {self.Q}, {N} and {H * W}")
+            cap_counts, cap_chars = export._capacity(0, B, N, H, W)  # segment ids are distinct within a frame
+            cap_chars = min(cap_chars, 2 ** 31 - 1)
+            head = torch.zeros((4 + N + 1 + 8 * N,), dtype=torch.int32, device=dev)  # totals | offsets | info
+            ws_bytes = _lib.lib().rgbd_rle_encode_workspace_size(0, B, N, H, W, cap_counts)
+            self._enc = dict(cap_counts=cap_counts, cap_chars=cap_chars, head=head,
+                             chars=torch.zeros((cap_chars,), dtype=torch.uint8, device=dev),
+                             ws=torch.empty((ws_bytes,), dtype=torch.uint8, device=dev),
+                             host=torch.empty((head.numel(),), dtype=torch.int32, pin_memory=True))
         self._th, self._tw = (ctypes.c_int * B)(*[H] * B), (ctypes.c_int * B)(*[W] * B)
         self._seg_ptrs = (ctypes.c_void_p * B)(*[self.segmentation[b].data_ptr() for b in range(B)])
         self._statuses = ()
@@ -255,6 +319,13 @@ class StreamingSegmenter:
                                      out=self.track_id)
             self._prev_seg.copy_(self.segmentation)
             self._prev_track.copy_(self.track_id)
+        if self._enc is not None:
+            e, N = self._enc, B * Q
+            head = e["head"]
+            _lib.check(L.rgbd_rle_encode_labels(_lib.RGBD_F32, ops._p(self.segmentation), B, self.H, self.W, Q,
+                                                ops._p(self.seg_id), Q, e["cap_counts"], e["cap_chars"],
+                                                ops._p(e["chars"]), ops._p(head[4:5 + N]), ops._p(head[5 + N:]),
+                                                ops._p(head[:4]), ops._p(e["ws"]), st), "rgbd_rle_encode_labels")
         if self.overlay_cfg is not None and self.overlay_cfg["color_by"] == "track":
             overlay_ops.track_lut(self.track_id, self._palette, out=self._lut)
         elif self.overlay_cfg is not None:
@@ -263,6 +334,8 @@ class StreamingSegmenter:
         if self.overlay_cfg is not None:
             overlay_ops.blend(self.rgb_u8, self.segmentation, self._lut, self.overlay_cfg["alpha"], out=self.overlay_u8)
         self._host.copy_(self._tables, non_blocking=True)
+        if self._enc is not None:
+            self._enc["host"].copy_(self._enc["head"], non_blocking=True)
 
     def capture(self):
         """Two eager warm-up runs on a side stream (weight packs, workspaces, device constants),
