@@ -905,33 +905,30 @@ int rgbd_colsum(int dtype, const void* y, int rows, int N, long long ld, float* 
  *   x_dtype / y_dtype: RGBD_F32 or RGBD_BF16 each (under torch.autocast a bf16 input gives a
  *   float32 output); gamma / beta float32 [C].  Statistics in float32, two passes over the
  *   register-resident row (C <= 1536).
+ * rgbd_layernorm_fwd, r == NULL: y = LN(x), any C <= 1536 and any alignment; r_dtype is ignored,
+ *   and s_out, y2 or clamp > 0 are RGBD_E_ARG.
+ * r != NULL: the post-norm residual LN(x + r) of the decoder / pixel-decoder encoder layers
+ *   (modeling_mask2former.py:1094-1101 / :1661-1683 `layer_norm(residual + hidden)`) in one pass:
+ *   s = x + r in float32 arithmetic, rounded to the promoted dtype (float32 when either is
+ *   float32, else bf16), written to s_out (required: the x of the backward), and y = LN(s); y2
+ *   (optional, bf16) receives y rounded to bf16 as well — the operand the consuming bf16 GEMMs
+ *   would otherwise cast from y.  clamp > 0: y = clamp(LN(s), -clamp, clamp) (the encoder layer's
+ *   clamp in training, :1094-1097; NaN kept).  C % 4 == 0 and 16-byte aligned x / r / s_out / y /
+ *   y2 (RGBD_E_SHAPE otherwise: the caller adds and normalises separately).
  * rgbd_layernorm_bwd: dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = gamma * dy,
  *   dx in x_dtype; dgamma = sum_rows dy * xhat, dbeta = sum_rows dy, float32 [C] (OVERWRITTEN;
- *   per-block partials in ws summed in block order: deterministic). */
-int rgbd_layernorm_fwd(int x_dtype, const void* x, const float* gamma, const float* beta, int rows, int C,
-                       float eps, int y_dtype, void* y, float* mean, float* rstd, void* stream);
-/* rgbd_add_layernorm_fwd: the post-norm residual LN(x + r) of the decoder / pixel-decoder encoder
- *   layers (modeling_mask2former.py:1094-1101 / :1661-1683 `layer_norm(residual + hidden)`) in one
- *   pass: s = x + r in float32 arithmetic, rounded to the promoted dtype (float32 when either is
- *   float32, else bf16), written to s_out (the input the backward's rgbd_layernorm_bwd takes),
- *   and y = LN(s) as rgbd_layernorm_fwd; y2 (optional, bf16) receives y rounded to bf16 as well —
- *   the operand the consuming bf16 GEMMs would otherwise cast from y.  clamp > 0: y =
- *   clamp(LN(s), -clamp, clamp) (the encoder layer's clamp in training, :1094-1097; NaN kept).
- *   C % 4 == 0, C <= 1536, 16-byte aligned x / r / s_out / y / y2 (RGBD_E_SHAPE otherwise: the
- *   caller adds and normalises separately).
- * rgbd_add_layernorm_bwd: rgbd_layernorm_bwd on s with the forward's clamp undone in the
- *   gradient (zero where clamp(y) != y, y recomputed in the forward's order) and ds_bf16
- *   (optional) = ds rounded to bf16 — the gradient the bf16 branch r receives. */
-int rgbd_add_layernorm_fwd(int x_dtype, const void* x, int r_dtype, const void* r, const float* gamma,
-                           const float* beta, int rows, int C, float eps, float clamp, int y_dtype, void* s_out,
-                           void* y, void* y2, float* mean, float* rstd, void* stream);
-int rgbd_add_layernorm_bwd(int s_dtype, const void* s_in, int dy_dtype, const void* dy, const float* gamma,
-                           const float* beta, const float* mean, const float* rstd, int rows, int C, float clamp,
-                           void* ds, void* ds_bf16, float* dgamma, float* dbeta, void* ws, void* stream);
+ *   per-block partials in ws summed in block order: deterministic).  clamp > 0 undoes the
+ *   forward's clamp in the gradient (dy counts as zero where clamp(y) != y, y recomputed from x,
+ *   gamma and beta, which may be NULL, in the forward's order); dx_bf16 (optional) = dx rounded to
+ *   bf16 — the gradient a bf16 branch r receives.  Either needs C % 4 == 0 and 16-byte aligned
+ *   x / dy / dx / dx_bf16 (RGBD_E_SHAPE otherwise). */
+int rgbd_layernorm_fwd(int x_dtype, const void* x, int r_dtype, const void* r, const float* gamma,
+                       const float* beta, int rows, int C, float eps, float clamp, int y_dtype, void* s_out,
+                       void* y, void* y2, float* mean, float* rstd, void* stream);
 size_t rgbd_layernorm_bwd_workspace_size(int rows, int C);
 int rgbd_layernorm_bwd(int x_dtype, const void* x, int dy_dtype, const void* dy, const float* gamma,
-                       const float* mean, const float* rstd, int rows, int C, void* dx, float* dgamma,
-                       float* dbeta, void* ws, void* stream);
+                       const float* beta, const float* mean, const float* rstd, int rows, int C, float clamp,
+                       void* dx, void* dx_bf16, float* dgamma, float* dbeta, void* ws, void* stream);
 
 /* f2 convolutions as GEMMs (csrc/conv.hip): the im2col operand of
  *   Y[b][o][p] = sum_k W[o][k] col[b][k][p] (+ bias[o])  (rgbd_gemm, RGBD_BIAS_M),

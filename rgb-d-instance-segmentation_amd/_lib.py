@@ -144,13 +144,10 @@ SIGNATURES = {
     "rgbd_im2col": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rgbd_colsum_workspace_size": (_SZ, [_I, _I]),
     "rgbd_colsum": (_I, [_I, _P, _I, _I, _LL, _P, _P, _P]),
-    "rgbd_layernorm_fwd": (_I, [_I, _P, _P, _P, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
-    "rgbd_add_layernorm_fwd": (_I, [_I, _P, _I, _P, _P, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P,
-                                    _P, _P, _P]),
-    "rgbd_add_layernorm_bwd": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P,
-                                    _P]),
+    "rgbd_layernorm_fwd": (_I, [_I, _P, _I, _P, _P, _P, _I, _I, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P, _P,
+                                _P, _P]),
     "rgbd_layernorm_bwd_workspace_size": (_SZ, [_I, _I]),
-    "rgbd_layernorm_bwd": (_I, [_I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "rgbd_layernorm_bwd": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "rgbd_groupnorm_workspace_size": (_SZ, [_I, _I]),
     "rgbd_groupnorm_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     "rgbd_groupnorm_bwd": (_I, [_I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -4,6 +4,8 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/rgbd_hip.h"
 
 #define RGBD_CHECK_LAUNCH()                                  \
@@ -150,6 +152,24 @@ __device__ __forceinline__ void vm_wait_barrier_dyn(int n) {
       vm_wait_barrier<23>();
       break;
   }
+}
+
+// Host-side typed dispatch: run-time codes to template arguments.  dispatch_dtype calls
+// f(type_c<T>{}) with T = float / bf16_t for RGBD_F32 / RGBD_BF16 (the caller has refused any other
+// code); dispatch_int<V...> calls f(std::integral_constant<int, V>{}) for the V that equals v (the
+// caller has refused a v outside the list: it would run the last V).  Both return what f returns.
+template <typename T>
+struct type_c {
+  using type = T;
+};
+template <typename F>
+auto dispatch_dtype(int code, F&& f) {
+  return code == RGBD_BF16 ? f(type_c<bf16_t>{}) : f(type_c<float>{});
+}
+template <int V0, int... Vs, typename F>
+auto dispatch_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }

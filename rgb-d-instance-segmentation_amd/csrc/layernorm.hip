@@ -159,11 +159,19 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-template <typename TX, typename TY, int T, int NCH>
-__global__ __launch_bounds__(256) void k_ln_fwd_v(const void* __restrict__ x, const float* __restrict__ gamma,
-                                                  const float* __restrict__ beta, int rows, int C, float eps,
-                                                  void* __restrict__ y, float* __restrict__ mean,
+// y = LN(x) (TR = void: r, clampc, s_out and y2 are not read), or the post-norm residual of the
+// decoder / pixel-decoder encoder layers in one pass:
+//   s = x + r (float32 arithmetic, rounded to s's dtype, as torch's add of the two), y = LN(s),
+//   clamped to +-clampc when clampc > 0 and written in bf16 to y2 as well when y2 is given;
+// s is written for the backward (rgbd_layernorm_bwd on s).
+template <typename TX, typename TR, typename TS, typename TY, int T, int NCH>
+__global__ __launch_bounds__(256) void k_ln_fwd_v(const void* __restrict__ x, const void* __restrict__ r,
+                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  int rows, int C, float eps, float clampc,
+                                                  void* __restrict__ s_out, void* __restrict__ y,
+                                                  bf16_t* __restrict__ y2, float* __restrict__ mean,
                                                   float* __restrict__ rstd) {
+  constexpr bool ADD = !std::is_void_v<TR>;
   const int j = threadIdx.x % T;
   const int row = blockIdx.x * (256 / T) + threadIdx.x / T;
   const bool live = row < rows;  // every lane of a group takes part in the shuffles
@@ -174,67 +182,18 @@ __global__ __launch_bounds__(256) void k_ln_fwd_v(const void* __restrict__ x, co
   for (int k = 0; k < NCH; ++k) {
     const int c = 4 * (j + T * k);
     if (c < C) {
-      ld4<TX>(x, base + c, v[k]);
-    } else {
-      v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0.f;
-    }
-    s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-  }
-  const float mu = group_sum<T>(s) / (float)C;
-  float q = 0.f;
+      if constexpr (ADD) {
+        float a[4], b[4];
+        ld4<TX>(x, base + c, a);
+        ld4<TR>(r, base + c, b);
 #pragma unroll
-  for (int k = 0; k < NCH; ++k)
-    if (4 * (j + T * k) < C)
+        for (int e = 0; e < 4; ++e) v[k][e] = a[e] + b[e];
+        if constexpr (sizeof(TS) == 2) {  // the bf16 sum is what the norm sees
 #pragma unroll
-      for (int e = 0; e < 4; ++e) q += (v[k][e] - mu) * (v[k][e] - mu);
-  const float var = group_sum<T>(q) / (float)C;
-  const float rs = 1.f / sqrtf(var + eps);
-  if (!live) return;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c = 4 * (j + T * k);
-    if (c < C) {
-      float o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        o[e] = (v[k][e] - mu) * rs * (gamma ? gamma[c + e] : 1.f) + (beta ? beta[c + e] : 0.f);
-      st4<TY>(y, base + c, o);
-    }
-  }
-  if (j == 0) {
-    mean[row] = mu;
-    rstd[row] = rs;
-  }
-}
-
-// The post-norm residual of the decoder / pixel-decoder encoder layers in one pass:
-//   s = x + r (float32 arithmetic, rounded to s's dtype, as torch's add of the two), y = LN(s);
-// s is written for the backward (rgbd_layernorm_bwd on s).  Same row grouping as k_ln_fwd_v.
-template <typename TX, typename TR, typename TS, typename TY, int T, int NCH>
-__global__ __launch_bounds__(256) void k_add_ln_fwd_v(const void* __restrict__ x, const void* __restrict__ r,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      int rows, int C, float eps, float clampc,
-                                                      void* __restrict__ s_out, void* __restrict__ y,
-                                                      bf16_t* __restrict__ y2, float* __restrict__ mean,
-                                                      float* __restrict__ rstd) {
-  const int j = threadIdx.x % T;
-  const int row = blockIdx.x * (256 / T) + threadIdx.x / T;
-  const bool live = row < rows;
-  const long long base = (long long)(live ? row : 0) * C;
-  float v[NCH][4];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int c = 4 * (j + T * k);
-    if (c < C) {
-      float a[4], b[4];
-      ld4<TX>(x, base + c, a);
-      ld4<TR>(r, base + c, b);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[k][e] = a[e] + b[e];
-      if constexpr (sizeof(TS) == 2) {  // the bf16 sum is what the norm sees
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[k][e] = bf16_to_f32(f32_to_bf16(v[k][e]));
+          for (int e = 0; e < 4; ++e) v[k][e] = bf16_to_f32(f32_to_bf16(v[k][e]));
+        }
+      } else {
+        ld4<TX>(x, base + c, v[k]);
       }
     } else {
       v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0.f;
@@ -255,17 +214,21 @@ __global__ __launch_bounds__(256) void k_add_ln_fwd_v(const void* __restrict__ x
   for (int k = 0; k < NCH; ++k) {
     const int c = 4 * (j + T * k);
     if (c < C) {
-      st4<TS>(s_out, base + c, v[k]);
+      if constexpr (ADD) st4<TS>(s_out, base + c, v[k]);
       float o[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         o[e] = (v[k][e] - mu) * rs * (gamma ? gamma[c + e] : 1.f) + (beta ? beta[c + e] : 0.f);
-      if (clampc > 0.f) {  // torch.clamp(y, -c, c): NaN stays NaN
+      if constexpr (ADD) {
+        if (clampc > 0.f) {  // torch.clamp(y, -c, c): NaN stays NaN
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] < -clampc ? -clampc : (o[e] > clampc ? clampc : o[e]);
+          for (int e = 0; e < 4; ++e) o[e] = o[e] < -clampc ? -clampc : (o[e] > clampc ? clampc : o[e]);
+        }
       }
       st4<TY>(y, base + c, o);
-      if (y2) st4<bf16_t>(y2, base + c, o);
+      if constexpr (ADD) {
+        if (y2) st4<bf16_t>(y2, base + c, o);
+      }
     }
   }
   if (j == 0) {
@@ -277,7 +240,7 @@ __global__ __launch_bounds__(256) void k_add_ln_fwd_v(const void* __restrict__ x
 // dx per row; dgamma / dbeta partials per block: part[blk][2][C].  A block's groups take rows
 // r0 + g, r0 + g + G, ... (G = groups per block), two rows per group in flight; the groups'
 // partials are summed in a fixed order through LDS: deterministic for a given shape.
-// Ext (rgbd_add_layernorm_bwd): with clampc > 0 the upstream gradient is masked where the
+// Ext (the backward of the fused LN(x + r)): with clampc > 0 the upstream gradient is masked where the
 // forward's clamp(y, -c, c) was not the identity (y recomputed from x, mean, rstd, gamma, beta in
 // the forward's operation order: the same bits); dx2 (optional) receives dx rounded to bf16.
 struct LnBwdExt {
@@ -421,101 +384,21 @@ inline int lnv_group(int C) {
   const int ch = C / 4;
   return ch <= 16 ? 16 : (ch <= 32 ? 32 : 64);
 }
-
-template <typename TX, typename TY, int T, int NCH>
-void lnv_fwd_launch(const void* x, const float* gamma, const float* beta, int rows, int C, float eps, void* y,
-                    float* mean, float* rstd, hipStream_t s) {
-  hipLaunchKernelGGL((k_ln_fwd_v<TX, TY, T, NCH>), dim3(ceil_div(rows, 256 / T)), dim3(256), 0, s, x, gamma, beta,
-                     rows, C, eps, y, mean, rstd);
+// the (T, NCH) instantiation of the vectorised kernels for C: f(T, NCH), both integral constants
+template <typename F>
+void lnv_dispatch(int C, F&& f) {
+  const int T = lnv_group(C);
+  if (T < 64) dispatch_int<16, 32>(T, [&](auto t) { f(t, std::integral_constant<int, 1>{}); });
+  else dispatch_int<1, 2, 3, 4, 5, 6>(ceil_div(C / 4, T), [&](auto n) { f(std::integral_constant<int, 64>{}, n); });
 }
-template <typename TX, typename TY>
-void lnv_fwd(const void* x, const float* gamma, const float* beta, int rows, int C, float eps, void* y, float* mean,
-             float* rstd, hipStream_t s) {
-  const int T = lnv_group(C), nch = ceil_div(C / 4, T);
-  if (T == 16) lnv_fwd_launch<TX, TY, 16, 1>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (T == 32) lnv_fwd_launch<TX, TY, 32, 1>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (nch == 1) lnv_fwd_launch<TX, TY, 64, 1>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (nch == 2) lnv_fwd_launch<TX, TY, 64, 2>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (nch == 3) lnv_fwd_launch<TX, TY, 64, 3>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (nch == 4) lnv_fwd_launch<TX, TY, 64, 4>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else if (nch == 5) lnv_fwd_launch<TX, TY, 64, 5>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else lnv_fwd_launch<TX, TY, 64, 6>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
+// The path of one call, decided once per entry point for the row kernel and the parameter
+// reduction alike: the vectorised kernels need C % 4 == 0 and 16-byte aligned rows (NULL counts as
+// aligned), the one-wave-per-row kernels take the rest.
+template <typename... P>
+bool lnv_path(int C, const P*... p) {
+  return lnv_ok(C) && ((((uintptr_t)p & 15) == 0) && ...);
 }
-template <typename TX, typename TD, int T, int NCH>
-void lnv_bwd_launch(const void* x, const void* dy, const float* gamma, const float* mean, const float* rstd, int rows,
-                    int C, void* dx, float* part, hipStream_t s, LnBwdExt ext = LnBwdExt{nullptr, 0.f, nullptr}) {
-  const int rb = lnv_rows_per_block(rows);
-  const size_t smem = (size_t)(256 / T) * 2 * C * sizeof(float);
-  hipLaunchKernelGGL((k_ln_bwd_v<TX, TD, T, NCH>), dim3(ceil_div(rows, rb)), dim3(256), smem, s, x, dy, gamma, mean,
-                     rstd, rows, C, rb, dx, part, ext);
-}
-template <typename TX, typename TD>
-void lnv_bwd(const void* x, const void* dy, const float* gamma, const float* mean, const float* rstd, int rows, int C,
-             void* dx, float* part, hipStream_t s, LnBwdExt ext = LnBwdExt{nullptr, 0.f, nullptr}) {
-  const int T = lnv_group(C), nch = ceil_div(C / 4, T);
-  if (T == 16) lnv_bwd_launch<TX, TD, 16, 1>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (T == 32) lnv_bwd_launch<TX, TD, 32, 1>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (nch == 1) lnv_bwd_launch<TX, TD, 64, 1>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (nch == 2) lnv_bwd_launch<TX, TD, 64, 2>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (nch == 3) lnv_bwd_launch<TX, TD, 64, 3>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (nch == 4) lnv_bwd_launch<TX, TD, 64, 4>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else if (nch == 5) lnv_bwd_launch<TX, TD, 64, 5>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-  else lnv_bwd_launch<TX, TD, 64, 6>(x, dy, gamma, mean, rstd, rows, C, dx, part, s, ext);
-}
-
-template <typename TX, typename TR, typename TS, typename TY, int T, int NCH>
-void add_lnv_launch(const void* x, const void* r, const float* gamma, const float* beta, int rows, int C, float eps,
-                    float clampc, void* s_out, void* y, bf16_t* y2, float* mean, float* rstd, hipStream_t s) {
-  hipLaunchKernelGGL((k_add_ln_fwd_v<TX, TR, TS, TY, T, NCH>), dim3(ceil_div(rows, 256 / T)), dim3(256), 0, s, x, r,
-                     gamma, beta, rows, C, eps, clampc, s_out, y, y2, mean, rstd);
-}
-template <typename TX, typename TR, typename TS, typename TY>
-void add_lnv(const void* x, const void* r, const float* gamma, const float* beta, int rows, int C, float eps,
-             float clampc, void* s_out, void* y, bf16_t* y2, float* mean, float* rstd, hipStream_t s) {
-  const int T = lnv_group(C), nch = ceil_div(C / 4, T);
-#define ADD_LNV(TT, NN) \
-  add_lnv_launch<TX, TR, TS, TY, TT, NN>(x, r, gamma, beta, rows, C, eps, clampc, s_out, y, y2, mean, rstd, s)
-  if (T == 16) ADD_LNV(16, 1);
-  else if (T == 32) ADD_LNV(32, 1);
-  else if (nch == 1) ADD_LNV(64, 1);
-  else if (nch == 2) ADD_LNV(64, 2);
-  else if (nch == 3) ADD_LNV(64, 3);
-  else if (nch == 4) ADD_LNV(64, 4);
-  else if (nch == 5) ADD_LNV(64, 5);
-  else ADD_LNV(64, 6);
-#undef ADD_LNV
-}
-
-template <typename TX>
-void ln_fwd_t(int y_dtype, const void* x, const float* gamma, const float* beta, int rows, int C, float eps, void* y,
-              float* mean, float* rstd, hipStream_t s) {
-  if (lnv_ok(C) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0) {
-    if (y_dtype == RGBD_BF16) lnv_fwd<TX, bf16_t>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-    else lnv_fwd<TX, float>(x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-    return;
-  }
-  dim3 grid(ceil_div(rows, 4));
-  if (y_dtype == RGBD_BF16)
-    hipLaunchKernelGGL((k_ln_fwd<TX, bf16_t>), grid, dim3(256), 0, s, x, gamma, beta, rows, C, eps, y, mean, rstd);
-  else
-    hipLaunchKernelGGL((k_ln_fwd<TX, float>), grid, dim3(256), 0, s, x, gamma, beta, rows, C, eps, y, mean, rstd);
-}
-
-template <typename TX>
-void ln_bwd_t(int dy_dtype, const void* x, const void* dy, const float* gamma, const float* mean, const float* rstd,
-              int rows, int C, void* dx, float* part, hipStream_t s) {
-  if (lnv_ok(C) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0) {
-    if (dy_dtype == RGBD_BF16) lnv_bwd<TX, bf16_t>(x, dy, gamma, mean, rstd, rows, C, dx, part, s);
-    else lnv_bwd<TX, float>(x, dy, gamma, mean, rstd, rows, C, dx, part, s);
-    return;
-  }
-  const int rb = ln_rows_per_block(rows);
-  dim3 grid(ceil_div(rows, rb));
-  if (dy_dtype == RGBD_BF16)
-    hipLaunchKernelGGL((k_ln_bwd<TX, bf16_t>), grid, dim3(256), 0, s, x, dy, gamma, mean, rstd, rows, C, rb, dx, part);
-  else
-    hipLaunchKernelGGL((k_ln_bwd<TX, float>), grid, dim3(256), 0, s, x, dy, gamma, mean, rstd, rows, C, rb, dx, part);
-}
+inline bool ln_dtype_ok(int d) { return d == RGBD_F32 || d == RGBD_BF16; }
 
 }  // namespace
 }  // namespace rgbd
@@ -524,73 +407,38 @@ using namespace rgbd;
 
 extern "C" {
 
-int rgbd_layernorm_fwd(int x_dtype, const void* x, const float* gamma, const float* beta, int rows, int C,
-                       float eps, int y_dtype, void* y, float* mean, float* rstd, void* stream) {
+int rgbd_layernorm_fwd(int x_dtype, const void* x, int r_dtype, const void* r, const float* gamma, const float* beta,
+                       int rows, int C, float eps, float clamp, int y_dtype, void* s_out, void* y, void* y2,
+                       float* mean, float* rstd, void* stream) {
   RGBD_REQUIRE(x && y && mean && rstd && rows > 0 && C > 0, RGBD_E_ARG);
+  RGBD_REQUIRE(r ? s_out != nullptr : !s_out && !y2 && !(clamp > 0.f), RGBD_E_ARG);
   RGBD_REQUIRE(C <= 64 * LN_MAXI, RGBD_E_SHAPE);
-  RGBD_REQUIRE((x_dtype == RGBD_F32 || x_dtype == RGBD_BF16) && (y_dtype == RGBD_F32 || y_dtype == RGBD_BF16),
-               RGBD_E_DTYPE);
+  const bool vec = lnv_path(C, x, r, s_out, y, y2);
+  RGBD_REQUIRE(vec || !r, RGBD_E_SHAPE);  // the fused sum has no one-wave-per-row kernel
+  RGBD_REQUIRE(ln_dtype_ok(x_dtype) && (!r || ln_dtype_ok(r_dtype)) && ln_dtype_ok(y_dtype), RGBD_E_DTYPE);
   hipStream_t s = (hipStream_t)stream;
-  if (x_dtype == RGBD_BF16)
-    ln_fwd_t<bf16_t>(y_dtype, x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  else
-    ln_fwd_t<float>(y_dtype, x, gamma, beta, rows, C, eps, y, mean, rstd, s);
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-int rgbd_add_layernorm_fwd(int x_dtype, const void* x, int r_dtype, const void* r, const float* gamma,
-                           const float* beta, int rows, int C, float eps, float clamp, int y_dtype, void* s_out,
-                           void* y, void* y2, float* mean, float* rstd, void* stream) {
-  RGBD_REQUIRE(x && r && s_out && y && mean && rstd && rows > 0 && C > 0, RGBD_E_ARG);
-  RGBD_REQUIRE(lnv_ok(C), RGBD_E_SHAPE);
-  RGBD_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)r & 15) == 0 && ((uintptr_t)s_out & 15) == 0 &&
-                   ((uintptr_t)y & 15) == 0 && ((uintptr_t)y2 & 15) == 0,
-               RGBD_E_SHAPE);
-  RGBD_REQUIRE((x_dtype == RGBD_F32 || x_dtype == RGBD_BF16) && (r_dtype == RGBD_F32 || r_dtype == RGBD_BF16) &&
-                   (y_dtype == RGBD_F32 || y_dtype == RGBD_BF16),
-               RGBD_E_DTYPE);
-  hipStream_t s = (hipStream_t)stream;
-  // s in the promoted dtype of x + r: float32 when either is
-#define ADD_LN(TX, TR, TS)                                                                      \
-  do {                                                                                          \
-    if (y_dtype == RGBD_BF16)                                                                   \
-      add_lnv<TX, TR, TS, bf16_t>(x, r, gamma, beta, rows, C, eps, clamp, s_out, y, (bf16_t*)y2, mean, rstd, s); \
-    else                                                                                        \
-      add_lnv<TX, TR, TS, float>(x, r, gamma, beta, rows, C, eps, clamp, s_out, y, (bf16_t*)y2, mean, rstd, s);  \
-  } while (0)
-  if (x_dtype == RGBD_F32 && r_dtype == RGBD_F32) ADD_LN(float, float, float);
-  else if (x_dtype == RGBD_F32) ADD_LN(float, bf16_t, float);
-  else if (r_dtype == RGBD_F32) ADD_LN(bf16_t, float, float);
-  else ADD_LN(bf16_t, bf16_t, bf16_t);
-#undef ADD_LN
-  RGBD_CHECK_LAUNCH();
-  return RGBD_OK;
-}
-
-int rgbd_add_layernorm_bwd(int s_dtype, const void* s_in, int dy_dtype, const void* dy, const float* gamma,
-                           const float* beta, const float* mean, const float* rstd, int rows, int C, float clamp,
-                           void* ds, void* ds_bf16, float* dgamma, float* dbeta, void* ws, void* stream) {
-  RGBD_REQUIRE(s_in && dy && mean && rstd && ds && dgamma && dbeta && ws && rows > 0 && C > 0, RGBD_E_ARG);
-  RGBD_REQUIRE(lnv_ok(C), RGBD_E_SHAPE);
-  RGBD_REQUIRE(((uintptr_t)s_in & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)ds & 15) == 0 &&
-                   ((uintptr_t)ds_bf16 & 15) == 0,
-               RGBD_E_SHAPE);
-  RGBD_REQUIRE((s_dtype == RGBD_F32 || s_dtype == RGBD_BF16) && (dy_dtype == RGBD_F32 || dy_dtype == RGBD_BF16),
-               RGBD_E_DTYPE);
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  const LnBwdExt ext{beta, clamp, (bf16_t*)ds_bf16};
-  if (s_dtype == RGBD_BF16) {
-    if (dy_dtype == RGBD_BF16) lnv_bwd<bf16_t, bf16_t>(s_in, dy, gamma, mean, rstd, rows, C, ds, part, s, ext);
-    else lnv_bwd<bf16_t, float>(s_in, dy, gamma, mean, rstd, rows, C, ds, part, s, ext);
-  } else {
-    if (dy_dtype == RGBD_BF16) lnv_bwd<float, bf16_t>(s_in, dy, gamma, mean, rstd, rows, C, ds, part, s, ext);
-    else lnv_bwd<float, float>(s_in, dy, gamma, mean, rstd, rows, C, ds, part, s, ext);
-  }
-  RGBD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_ln_param_reduce_v, dim3(ceil_div(2 * C, 64)), dim3(1024), 0, s, part,
-                     ceil_div(rows, lnv_rows_per_block(rows)), C, dgamma, dbeta);
+  dispatch_dtype(x_dtype, [&](auto tx) {
+    dispatch_dtype(y_dtype, [&](auto ty) {
+      using TX = typename decltype(tx)::type;
+      using TY = typename decltype(ty)::type;
+      if (!vec) {
+        k_ln_fwd<TX, TY><<<ceil_div(rows, 4), 256, 0, s>>>(x, gamma, beta, rows, C, eps, y, mean, rstd);
+        return;
+      }
+      auto launch = [&](auto tr) {
+        using TR = typename decltype(tr)::type;
+        // s in the promoted dtype of x + r: float32 when either is (the plain norm writes no s)
+        using TS = std::conditional_t<std::is_same_v<TR, float>, float, TX>;
+        lnv_dispatch(C, [&](auto t, auto n) {
+          constexpr int T = decltype(t)::value, NCH = decltype(n)::value;
+          k_ln_fwd_v<TX, TR, TS, TY, T, NCH><<<ceil_div(rows, 256 / T), 256, 0, s>>>(
+              x, r, gamma, beta, rows, C, eps, clamp, s_out, y, (bf16_t*)y2, mean, rstd);
+        });
+      };
+      if (r) dispatch_dtype(r_dtype, launch);
+      else launch(type_c<void>{});
+    });
+  });
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }
@@ -602,26 +450,36 @@ size_t rgbd_layernorm_bwd_workspace_size(int rows, int C) {
 }
 
 int rgbd_layernorm_bwd(int x_dtype, const void* x, int dy_dtype, const void* dy, const float* gamma,
-                       const float* mean, const float* rstd, int rows, int C, void* dx, float* dgamma,
-                       float* dbeta, void* ws, void* stream) {
+                       const float* beta, const float* mean, const float* rstd, int rows, int C, float clamp,
+                       void* dx, void* dx_bf16, float* dgamma, float* dbeta, void* ws, void* stream) {
   RGBD_REQUIRE(x && dy && mean && rstd && dx && dgamma && dbeta && ws && rows > 0 && C > 0, RGBD_E_ARG);
   RGBD_REQUIRE(C <= 64 * LN_MAXI, RGBD_E_SHAPE);
-  RGBD_REQUIRE((x_dtype == RGBD_F32 || x_dtype == RGBD_BF16) && (dy_dtype == RGBD_F32 || dy_dtype == RGBD_BF16),
-               RGBD_E_DTYPE);
+  const bool vec = lnv_path(C, x, dy, dx, dx_bf16);
+  RGBD_REQUIRE(vec || (!(clamp > 0.f) && !dx_bf16), RGBD_E_SHAPE);  // only k_ln_bwd_v has the Ext arms
+  RGBD_REQUIRE(ln_dtype_ok(x_dtype) && ln_dtype_ok(dy_dtype), RGBD_E_DTYPE);
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)ws;
-  if (x_dtype == RGBD_BF16)
-    ln_bwd_t<bf16_t>(dy_dtype, x, dy, gamma, mean, rstd, rows, C, dx, part, s);
-  else
-    ln_bwd_t<float>(dy_dtype, x, dy, gamma, mean, rstd, rows, C, dx, part, s);
+  const int rb = vec ? lnv_rows_per_block(rows) : ln_rows_per_block(rows);
+  const int nblk = ceil_div(rows, rb);
+  dispatch_dtype(x_dtype, [&](auto tx) {
+    dispatch_dtype(dy_dtype, [&](auto td) {
+      using TX = typename decltype(tx)::type;
+      using TD = typename decltype(td)::type;
+      if (!vec) {
+        k_ln_bwd<TX, TD><<<nblk, 256, 0, s>>>(x, dy, gamma, mean, rstd, rows, C, rb, dx, part);
+        return;
+      }
+      lnv_dispatch(C, [&](auto t, auto n) {
+        constexpr int T = decltype(t)::value, NCH = decltype(n)::value;
+        const size_t smem = (size_t)(256 / T) * 2 * C * sizeof(float);
+        k_ln_bwd_v<TX, TD, T, NCH><<<nblk, 256, smem, s>>>(x, dy, gamma, mean, rstd, rows, C, rb, dx, part,
+                                                          LnBwdExt{beta, clamp, (bf16_t*)dx_bf16});
+      });
+    });
+  });
   RGBD_CHECK_LAUNCH();
-  const bool vec = lnv_ok(C) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(k_ln_param_reduce_v, dim3(ceil_div(2 * C, 64)), dim3(1024), 0, s, part,
-                       ceil_div(rows, lnv_rows_per_block(rows)), C, dgamma, dbeta);
-  else
-    hipLaunchKernelGGL(k_ln_param_reduce, dim3(ceil_div(2 * C, 256)), dim3(256), 0, s, part,
-                       ceil_div(rows, ln_rows_per_block(rows)), C, dgamma, dbeta);
+  if (vec) k_ln_param_reduce_v<<<ceil_div(2 * C, 64), 1024, 0, s>>>(part, nblk, C, dgamma, dbeta);
+  else k_ln_param_reduce<<<ceil_div(2 * C, 256), 256, 0, s>>>(part, nblk, C, dgamma, dbeta);
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }

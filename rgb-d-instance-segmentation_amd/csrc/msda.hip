@@ -516,6 +516,12 @@ __global__ __launch_bounds__(256) void k_msda_loc_bwd(const float* __restrict__ 
   goff[i] = Num<T>::from_f(g / norm[2 * l + c]);
 }
 
+// the (value dtype, head width D) instantiation of an entry point's launcher: f(type_c<T>, D)
+template <typename F>
+auto msda_dispatch(int dtype, int D, F&& f) {
+  return dispatch_dtype(dtype, [&](auto t) { return dispatch_int<16, 32, 64>(D, [&](auto d) { return f(t, d); }); });
+}
+
 }  // namespace
 }  // namespace rgbd
 
@@ -533,15 +539,9 @@ extern "C" int rgbd_msda_fwd(int dtype, const void* value, int B, int L, const i
   if (rc) return rc;
   const long long nqh = (long long)B * Q * NH;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == RGBD_F32) {
-    if (D == 32) launch_fwd<float, 32>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-    else if (D == 64) launch_fwd<float, 64>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-    else launch_fwd<float, 16>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-  } else {
-    if (D == 32) launch_fwd<bf16_t, 32>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-    else if (D == 64) launch_fwd<bf16_t, 64>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-    else launch_fwd<bf16_t, 16>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
-  }
+  msda_dispatch(dtype, D, [&](auto t, auto d) {
+    launch_fwd<typename decltype(t)::type, decltype(d)::value>(value, lv, S, Q, NH, P, loc, attw, nqh, out, s);
+  });
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }
@@ -560,16 +560,10 @@ extern "C" int rgbd_msda_bwd(int dtype, const void* value, int B, int L, const i
   const int rc = msda_levels(L, shapes_host, lv, S);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int r;
-  if (dtype == RGBD_F32) {
-    if (D == 32) r = launch_bwd<float, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-    else if (D == 64) r = launch_bwd<float, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-    else r = launch_bwd<float, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-  } else {
-    if (D == 32) r = launch_bwd<bf16_t, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-    else if (D == 64) r = launch_bwd<bf16_t, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-    else r = launch_bwd<bf16_t, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, gvalue, gloc, gattw, s);
-  }
+  const int r = msda_dispatch(dtype, D, [&](auto t, auto d) {
+    return launch_bwd<typename decltype(t)::type, decltype(d)::value>(value, lv, B, S, Q, NH, P, loc, attw, gout,
+                                                                       gvalue, gloc, gattw, s);
+  });
   if (r != RGBD_OK) return r;
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
@@ -591,15 +585,10 @@ extern "C" int rgbd_msda_bwd_emit(int dtype, const void* value, int B, int L, co
   RGBD_REQUIRE((long long)B * NH * S <= 0x7ffffffell, RGBD_E_SHAPE);
   RGBD_REQUIRE((long long)B * NH * Q * L * P * 4 <= 0x7ffffffell, RGBD_E_SHAPE);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == RGBD_F32) {
-    if (D == 32) launch_emit<float, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-    else if (D == 64) launch_emit<float, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-    else launch_emit<float, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-  } else {
-    if (D == 32) launch_emit<bf16_t, 32>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-    else if (D == 64) launch_emit<bf16_t, 64>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-    else launch_emit<bf16_t, 16>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef, gloc, gattw, s);
-  }
+  msda_dispatch(dtype, D, [&](auto t, auto d) {
+    launch_emit<typename decltype(t)::type, decltype(d)::value>(value, lv, B, S, Q, NH, P, loc, attw, gout, keys, coef,
+                                                                gloc, gattw, s);
+  });
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }
@@ -616,15 +605,10 @@ extern "C" int rgbd_msda_bwd_gather(int dtype, const int* sorted_keys, const lon
   RGBD_REQUIRE(ntaps <= 0x7ffffffell, RGBD_E_SHAPE);
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)ntaps;
-  if (dtype == RGBD_F32) {
-    if (D == 32) launch_gather<float, 32>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-    else if (D == 64) launch_gather<float, 64>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-    else launch_gather<float, 16>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-  } else {
-    if (D == 32) launch_gather<bf16_t, 32>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-    else if (D == 64) launch_gather<bf16_t, 64>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-    else launch_gather<bf16_t, 16>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH, LP, gvalue, s);
-  }
+  msda_dispatch(dtype, D, [&](auto t, auto d) {
+    launch_gather<typename decltype(t)::type, decltype(d)::value>(sorted_keys, sorted_idx, n, coef, gout, B, S, Q, NH,
+                                                                  LP, gvalue, s);
+  });
   RGBD_CHECK_LAUNCH();
   return RGBD_OK;
 }

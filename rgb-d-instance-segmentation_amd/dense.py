@@ -317,48 +317,70 @@ class GeluFFNFunction(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2, gy if ctx.needs_input_grad[5] else None, None, None
 
 
+def _ln_rows(t, align):
+    """t as contiguous [rows, C] in a kernel dtype (any other is computed in float32); with
+    ``align`` a copy where the data is not 16-byte aligned (the fused kernels' row accesses)."""
+    t2 = t.reshape(-1, t.shape[-1])
+    if t2.dtype not in _CODE:
+        t2 = t2.float()
+    t2 = t2.contiguous()
+    return t2.clone() if align and t2.data_ptr() % 16 else t2
+
+
+def _ln_forward(x, r, gamma, beta, eps, clamp, y_dtype, twin):
+    """rgbd_layernorm_fwd on the rows of x (r given: of x + r, the fused form).  Returns the
+    backward's input (x as rows, or the sum), y as rows, its bf16 twin or None, and what the
+    backward needs besides: gamma / beta in float32, mean, rstd."""
+    x2 = _ln_rows(x, r is not None)
+    r2 = None if r is None else _ln_rows(r, True)
+    rows, C = x2.shape
+    dev = x.device
+    s = None if r is None else torch.empty((rows, C), dtype=torch.promote_types(x2.dtype, r2.dtype), device=dev)
+    y = torch.empty((rows, C), dtype=y_dtype, device=dev)
+    y2 = torch.empty((rows, C), dtype=torch.bfloat16, device=dev) if twin else None
+    mean = torch.empty((rows,), dtype=torch.float32, device=dev)
+    rstd = torch.empty_like(mean)
+    g32 = None if gamma is None else gamma.detach().float().contiguous()
+    b32 = None if beta is None else beta.detach().float().contiguous()
+    check(_lib.lib().rgbd_layernorm_fwd(_CODE[x2.dtype], _p(x2), 0 if r is None else _CODE[r2.dtype], _p(r2), _p(g32),
+                                        _p(b32), rows, C, float(eps), float(clamp), _CODE[y_dtype], _p(s), _p(y),
+                                        _p(y2), _p(mean), _p(rstd), _stream(dev)), "rgbd_layernorm_fwd")
+    return (x2 if r is None else s), y, y2, g32, b32, mean, rstd
+
+
+def _ln_backward(gy, x2, g32, b32, mean, rstd, clamp=0.0, twin=False, align=False):
+    """rgbd_layernorm_bwd: dx (x2's dtype), its bf16 twin or None, dgamma, dbeta."""
+    rows, C = x2.shape
+    g2 = _ln_rows(gy.reshape(rows, C), align)
+    dx = torch.empty_like(x2)
+    dx2 = torch.empty((rows, C), dtype=torch.bfloat16, device=x2.device) if twin else None
+    dg = torch.empty((C,), dtype=torch.float32, device=x2.device)
+    db = torch.empty_like(dg)
+    L = _lib.lib()
+    ws = _workspace(x2.device, L.rgbd_layernorm_bwd_workspace_size(rows, C), "ln_bwd")
+    check(L.rgbd_layernorm_bwd(_CODE[x2.dtype], _p(x2), _CODE[g2.dtype], _p(g2), _p(g32), _p(b32), _p(mean), _p(rstd),
+                               rows, C, float(clamp), _p(dx), _p(dx2), _p(dg), _p(db), _p(ws), _stream(x2.device)),
+          "rgbd_layernorm_bwd")
+    return dx, dx2, dg, db
+
+
 class LayerNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, y_dtype):
-        C = x.shape[-1]
-        x2 = x.reshape(-1, C)
-        if x2.dtype not in _CODE:
-            x2 = x2.float()
-        x2 = x2.contiguous()
-        rows = x2.shape[0]
-        y = torch.empty((rows, C), dtype=y_dtype, device=x.device)
-        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        g32 = None if gamma is None else gamma.detach().float().contiguous()
-        b32 = None if beta is None else beta.detach().float().contiguous()
-        check(_lib.lib().rgbd_layernorm_fwd(_CODE[x2.dtype], _p(x2), _p(g32), _p(b32), rows, C, float(eps),
-                                            _CODE[y_dtype], _p(y), _p(mean), _p(rstd), _stream(x.device)),
-              "rgbd_layernorm_fwd")
-        ctx.save_for_backward(x2, g32, mean, rstd)
+        x2, y, _, g32, b32, mean, rstd = _ln_forward(x, None, gamma, beta, eps, 0.0, y_dtype, False)
+        ctx.save_for_backward(x2, g32, b32, mean, rstd)
         ctx.x_dtype, ctx.has_g, ctx.has_b = x.dtype, gamma is not None, beta is not None
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, gy):
-        x2, g32, mean, rstd = ctx.saved_tensors
-        rows, C = x2.shape
-        g2 = gy.reshape(rows, C)
-        if g2.dtype not in _CODE:
-            g2 = g2.float()
-        g2 = g2.contiguous()
-        dx = torch.empty_like(x2)
-        dg = torch.empty((C,), dtype=torch.float32, device=x2.device)
-        db = torch.empty_like(dg)
-        L = _lib.lib()
-        ws = _workspace(x2.device, L.rgbd_layernorm_bwd_workspace_size(rows, C), "ln_bwd")
-        check(L.rgbd_layernorm_bwd(_CODE[x2.dtype], _p(x2), _CODE[g2.dtype], _p(g2), _p(g32), _p(mean), _p(rstd),
-                                   rows, C, _p(dx), _p(dg), _p(db), _p(ws), _stream(x2.device)), "rgbd_layernorm_bwd")
+        dx, _, dg, db = _ln_backward(gy, *ctx.saved_tensors)
         return (dx.to(ctx.x_dtype).view(gy.shape), dg if ctx.has_g else None, db if ctx.has_b else None, None, None)
 
 
 class AddLayerNormFunction(torch.autograd.Function):
     """y = LayerNorm(x + r) (then clamp(y, -clamp, clamp) when clamp > 0): the sum, the norm and
-    the clamp in one kernel (rgbd_add_layernorm_fwd), the sum kept for the backward; its gradient
+    the clamp in one kernel (rgbd_layernorm_fwd with r), the sum kept for the backward; its gradient
     goes to x and r in their own dtypes (what autograd's add backward hands each: the same values,
     the bf16 one written by the backward kernel itself).  With ``twin`` a second, non-
     differentiable output holds y in bf16 (the consuming GEMMs' operand)."""
@@ -366,24 +388,7 @@ class AddLayerNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, r, gamma, beta, eps, y_dtype, twin, clamp):
         ctx.set_materialize_grads(False)
-        C = x.shape[-1]
-        x2 = x.reshape(-1, C).contiguous()
-        r2 = r.reshape(-1, C).contiguous()
-        x2 = x2 if x2.data_ptr() % 16 == 0 else x2.clone()  # the kernel's 16-byte row accesses
-        r2 = r2 if r2.data_ptr() % 16 == 0 else r2.clone()
-        rows = x2.shape[0]
-        s_dtype = torch.promote_types(x2.dtype, r2.dtype)
-        s = torch.empty((rows, C), dtype=s_dtype, device=x.device)
-        y = torch.empty((rows, C), dtype=y_dtype, device=x.device)
-        y2 = torch.empty((rows, C), dtype=torch.bfloat16, device=x.device) if twin else None
-        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        g32 = None if gamma is None else gamma.detach().float().contiguous()
-        b32 = None if beta is None else beta.detach().float().contiguous()
-        check(_lib.lib().rgbd_add_layernorm_fwd(_CODE[x2.dtype], _p(x2), _CODE[r2.dtype], _p(r2), _p(g32), _p(b32),
-                                                rows, C, float(eps), float(clamp), _CODE[y_dtype], _p(s), _p(y),
-                                                _p(y2), _p(mean), _p(rstd), _stream(x.device)),
-              "rgbd_add_layernorm_fwd")
+        s, y, y2, g32, b32, mean, rstd = _ln_forward(x, r, gamma, beta, eps, clamp, y_dtype, twin)
         ctx.save_for_backward(s, g32, b32, mean, rstd)
         ctx.dtypes, ctx.has_g, ctx.has_b, ctx.clamp = (x.dtype, r.dtype), gamma is not None, beta is not None, clamp
         if y2 is None:
@@ -393,26 +398,11 @@ class AddLayerNormFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gy2):
-        s, g32, b32, mean, rstd = ctx.saved_tensors
-        rows, C = s.shape
         if gy is None:
             return None, None, None, None, None, None, None, None
-        g2 = gy.reshape(rows, C)
-        if g2.dtype not in _CODE:
-            g2 = g2.float()
-        g2 = g2.contiguous()
-        if g2.data_ptr() % 16:
-            g2 = g2.clone()
-        ds = torch.empty_like(s)
+        s = ctx.saved_tensors[0]
         twin = s.dtype == torch.float32 and ctx.dtypes[1] == torch.bfloat16
-        ds2 = torch.empty((rows, C), dtype=torch.bfloat16, device=s.device) if twin else None
-        dg = torch.empty((C,), dtype=torch.float32, device=s.device)
-        db = torch.empty_like(dg)
-        L = _lib.lib()
-        ws = _workspace(s.device, L.rgbd_layernorm_bwd_workspace_size(rows, C), "ln_bwd")
-        check(L.rgbd_add_layernorm_bwd(_CODE[s.dtype], _p(s), _CODE[g2.dtype], _p(g2), _p(g32), _p(b32), _p(mean),
-                                       _p(rstd), rows, C, float(ctx.clamp), _p(ds), _p(ds2), _p(dg), _p(db), _p(ws),
-                                       _stream(s.device)), "rgbd_add_layernorm_bwd")
+        ds, ds2, dg, db = _ln_backward(gy, *ctx.saved_tensors, ctx.clamp, twin, align=True)
         ds = ds.view(gy.shape)
         dr = ds2.view(gy.shape) if twin else ds.to(ctx.dtypes[1])
         return (ds.to(ctx.dtypes[0]), dr, dg if ctx.has_g else None, db if ctx.has_b else None,

@@ -71,6 +71,44 @@ def test_dsam_run_calls_argument_validation_without_device():
                                   null) == -1
 
 
+def test_layernorm_argument_validation_without_device():
+    """The two LayerNorm calls (one per pass; r == NULL is the plain norm): what does not go with
+    the plain norm is RGBD_E_ARG, what the fused sum or the backward's clamp / bf16 twin need of C
+    and the pointers' alignment RGBD_E_SHAPE, an unknown dtype RGBD_E_DTYPE — nothing launched."""
+    L = _lib.lib()
+    null, fake, odd = ctypes.c_void_p(0), ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1008)
+    f32 = _lib.RGBD_F32
+
+    def fwd(x=fake, r=null, C=256, clamp=0.0, s_out=null, y2=null, x_dtype=f32, r_dtype=f32, y_dtype=f32):
+        return L.rgbd_layernorm_fwd(x_dtype, x, r_dtype, r, fake, fake, 37, C, 1e-5, clamp, y_dtype, s_out, fake, y2,
+                                    fake, fake, null)
+
+    def bwd(C=256, clamp=0.0, dx_bf16=null, x_dtype=f32, dy_dtype=f32, dx=fake):
+        return L.rgbd_layernorm_bwd(x_dtype, fake, dy_dtype, fake, fake, null, fake, fake, 37, C, clamp, dx, dx_bf16,
+                                    fake, fake, fake, null)
+
+    assert fwd(s_out=fake) == -1 and fwd(y2=fake) == -1 and fwd(clamp=1.0) == -1  # r == NULL: the plain norm
+    assert fwd(r=fake) == -1                                                        # r needs s_out
+    assert fwd(x=null) == -1 and bwd(dx=null) == -1
+    assert fwd(r=fake, s_out=fake, C=1002) == -2
+    assert fwd(x=odd, r=fake, s_out=fake) == -2
+    assert fwd(r=fake, s_out=fake, y2=odd) == -2
+    assert fwd(C=1540) == -2 and fwd(r=fake, s_out=fake, C=1540) == -2 and bwd(C=1540) == -2
+    assert fwd(x_dtype=7) == -3 and fwd(y_dtype=7) == -3 and fwd(r=fake, s_out=fake, r_dtype=7) == -3
+    assert bwd(x_dtype=7) == -3 and bwd(dy_dtype=7) == -3
+    assert bwd(C=1002, clamp=1.0) == -2
+    assert bwd(C=1002, dx_bf16=fake) == -2
+    assert bwd(dx_bf16=odd) == -2
+
+
+def test_add_layernorm_entry_points_are_gone():
+    """rgbd_layernorm_fwd / _bwd took over the fused calls: header, ctypes table and library."""
+    L = _lib.lib()
+    for name in ("rgbd_add_layernorm_fwd", "rgbd_add_layernorm_bwd"):
+        assert name not in _lib.header_symbols() and name not in _lib.SIGNATURES and not hasattr(L, name)
+    assert len(_lib.SIGNATURES) == 126
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from rgbd_amd import ops

@@ -182,12 +182,19 @@ def test_colsum():
         assert torch.equal(dense.colsum(y), first)  # deterministic, tickets rearmed
 
 
+# one C per (T, NCH) arm of the vectorised dispatch, each with a ragged last chunk: T16, T32, T64 x 1 .. 6
+LNV_ARMS = [60, 100, 252, 508, 764, 1020, 1276, 1532]
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("C,rows", [(96, 333), (96, 20000), (192, 4097), (256, 333), (384, 3333), (768, 333),
-                                    (1536, 700), (1000, 333), (60, 777)])
+                                    (1536, 700), (1000, 333), (60, 777), (62, 37), (1002, 37), (1534, 37)]
+                         + [(C, 37) for C in LNV_ARMS])
 def test_layernorm_fwd_bwd(dt, C, rows):
-    """C % 4 == 0: the vectorised row-group kernels (many rows per wave, block partials of the
-    parameter gradients); C = 1000 / 60: the one-wave-per-row kernels."""
+    """C % 4 == 0 (1000 and 60 included): the vectorised row-group kernels (many rows per wave,
+    block partials of the parameter gradients), every dispatch arm at rows = 37 (ragged against
+    every rows-per-block; three backward blocks, an odd count for the two-rows-in-flight loop);
+    C = 62 / 1002 / 1534: the one-wave-per-row kernels (1534 fills the last register slot partly)."""
     from rgbd_amd import dense
     g = torch.Generator(device="cpu").manual_seed(C)
     ln = torch.nn.LayerNorm(C, eps=1e-5).to(DEV)
@@ -227,11 +234,12 @@ def test_gemm_bf16_rounded_float32_store(a_t, b_t, M, N, K, act):
 
 @pytest.mark.parametrize("xdt,rdt", [(torch.float32, torch.float32), (torch.float32, torch.bfloat16),
                                      (torch.bfloat16, torch.bfloat16)], ids=["f32+f32", "f32+bf16", "bf16+bf16"])
-@pytest.mark.parametrize("C,rows", [(256, 800), (256, 50400), (96, 333), (1536, 70)])
+@pytest.mark.parametrize("C,rows", [(256, 800), (256, 50400), (96, 333), (1536, 70)] + [(C, 37) for C in LNV_ARMS])
 def test_add_layernorm_fused(xdt, rdt, C, rows):
     """LN(x + r) in one kernel (the decoder / encoder layers' post-norm residual): the sum in the
     promoted dtype exactly as torch's add (bitwise), the norm and every gradient against float64
-    (x and r each get the sum's gradient in their own dtype)."""
+    (x and r each get the sum's gradient in their own dtype); the plain norm of the sum gives the
+    same bits on every dispatch arm of the kernel the two share."""
     from rgbd_amd import dense
     g = torch.Generator(device="cpu").manual_seed(C + rows)
     ln = dense.HipLayerNorm(C, eps=1e-5).to(DEV)

@@ -201,7 +201,8 @@ def test_colsum(dt, rows, N):
 
 
 @pytest.mark.parametrize("dt", [F32, BF16], ids=DT_IDS)
-@pytest.mark.parametrize("C,rows", [(60, 777), (1000, 333), (96, 333)])
+# C = 62 / 1002 (no multiple of 4): the one-wave-per-row kernels
+@pytest.mark.parametrize("C,rows", [(60, 777), (1000, 333), (96, 333), (62, 37), (1002, 37)])
 def test_layer_norm_fwd_bwd(dt, C, rows):
     from rgbd_amd import dense
     g = torch.Generator().manual_seed(C)
